@@ -30,11 +30,19 @@ layouts are (layout_plan):
     rank's pass).
 The timed regions are bracketed by barriers and the max over ranks is used.
 
-Extra fields on the JSON line: "roofline" for the dominant kernel (the
-fp16 MFMA screen, ip_scan_ws_kernel), "cpu_baseline" (the oracle's per-user
+A plain run (no --full) sets up, warms up, times the --steps steps, writes
+the last step's outputs if --dump-outputs DIR is given, and prints the JSON
+line: the headline fields, "phase_ms" and "roofline" for the dominant kernel
+(the fp16 MFMA screen, ip_scan_ws_kernel; HIP events inside the timed steps).
+
+With --full the run also measures, after the headline, what takes runs of its
+own, and reports it as extra fields: "cpu_baseline" (the oracle's per-user
 exact scan -- the reference's nq=1 IndexFlatIP shape -- on a bounded user
-sample, rank 0, N=1), "din" (BASELINE config 3, DIN scored pairs/s),
-"itemcf" and "plugins" (N=1 only).
+sample, rank 0, N=1, with a spot check of the timed outputs against the
+oracle), "din" (BASELINE config 3, DIN scored pairs/s), "itemcf" and
+"plugins" (N=1 only), "config4" (N>1).  --no-cpu-baseline, --no-din,
+--no-itemcf, --no-plugins and --no-config4 drop single legs of a --full run;
+without --full those fields are null.
 """
 from __future__ import annotations
 
@@ -155,6 +163,37 @@ def log(*a):
     # print's separate text / newline writes could interleave between ranks
     sys.stderr.write(" ".join(str(x) for x in a) + "\n")
     sys.stderr.flush()
+
+
+DUMP_BUDGET_BYTES = 48_000_000  # --dump-outputs: all files together stay well under 64 MB
+
+
+def dump_rows(n_rows: int, row_bytes: int, budget: int = DUMP_BUDGET_BYTES):
+    """The rows of the per-row outputs that --dump-outputs writes: every row
+    when they fit into ``budget`` bytes, else a fixed sample (seed 0, sorted,
+    no repeats) -- the same rows for the same sizes, so that two builds can be
+    compared output for output.  None stands for every row."""
+    fit = budget // max(1, row_bytes)
+    if n_rows <= fit:
+        return None
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=fit, replace=False))
+
+
+def dump_outputs(path, outputs, budget: int = DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: write what the timed path computed in its last step
+    -- ``outputs``: name -> device tensor with one row per user -- as
+    DIR/<name>.npy in float32 (integer item rows are exact in float32: they
+    are below 2^24), sampled by dump_rows."""
+    os.makedirs(path, exist_ok=True)
+    n_rows = {int(t.shape[0]) for t in outputs.values()}
+    assert len(n_rows) == 1, n_rows
+    rows = dump_rows(n_rows.pop(), sum(4 * int(t[0].numel()) for t in outputs.values()), budget)
+    idx = None if rows is None else torch.from_numpy(rows).to(next(iter(outputs.values())).device)
+    for name, t in outputs.items():
+        assert t.dtype == torch.float32 or (not t.dtype.is_floating_point and int(t.max()) < 2 ** 24), (name, t.dtype)
+        a = (t if idx is None else t.index_select(0, idx)).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return rows
 
 
 def recall_workload(seed: int, n_users: int, n_items: int, dim: int, device):
@@ -514,6 +553,7 @@ def run_fused(args, device, rank, world, dist):
         fused.rank(s, r, probs)
         if ev is not None:
             ev[2].record()
+        return s, r
 
     for _ in range(args.warmup):
         step()
@@ -524,13 +564,15 @@ def run_fused(args, device, rank, world, dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(evs[i])
+        last = step(evs[i])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     el = time.perf_counter() - t0
     if dist is not None:
         el = max_over_ranks(el, device)
+    if args.dump_outputs and rank == 0:  # rank 0's users
+        dump_outputs(args.dump_outputs, {"scores": last[0], "rows": last[1], "probs": probs.view(U, k)})
     rec_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
     din_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
     pairs = U * k * world
@@ -842,6 +884,12 @@ def main(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous only, no workload")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the CPU baselines and the "
+                         "oracle spot check, DIN (config 3), ItemCF, the plugin entry points, config 4 at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (user vectors, top-k scores and item rows; a fixed "
+                         "seeded sample of the users when they exceed 48 MB) as DIR/<name>.npy, float32")
     ap.add_argument("--users", type=int, default=250_000)
     ap.add_argument("--items", type=int, default=364_047)
     ap.add_argument("--dim", type=int, default=32)
@@ -877,6 +925,8 @@ def main(argv=None):
     ap.add_argument("--din-warmup", type=int, default=2)
     ap.add_argument("--din-cpu-sample", type=int, default=4096)
     args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_din = args.no_itemcf = args.no_plugins = args.no_config4 = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, argv))
@@ -1014,7 +1064,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         t_start = time.perf_counter()
         for i in range(args.steps):
-            step(evs[i])
+            last = step(evs[i])
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -1062,7 +1112,11 @@ def main(argv=None):
         return {"step": step, "plan": plan, "catalog": catalog_mode, "value": value, "ms_step": ms_step,
                 "tower_ms": tower_ms, "screen_ms": screen_ms, "finish_ms": finish_ms, "refine_ms": refine_ms,
                 "scan_ms": scan_ms, "select_ms": select_ms, "roofline": roofline,
-                "item_vec": item_vec, "out_r": None if catalog_mode else out_r, "U": U, "I": I, "D": D, "K": K}
+                "item_vec": item_vec, "out_r": None if catalog_mode else out_r, "U": U, "I": I, "D": D, "K": K,
+                # what a caller of the timed path receives, from the last timed step: the user
+                # vectors with the top-k scores and item rows (config 4: this rank's user block)
+                "outputs": ({"topk_scores": last[0], "topk_rows": last[1]} if catalog_mode else
+                            {"user_vec": last, "topk_scores": out_s, "topk_rows": out_r})}
 
     U, I, D, K = args.users, args.items, args.dim, args.topk + 1
     rec = run_recall("single" if world == 1 else args.shard)
@@ -1070,6 +1124,10 @@ def main(argv=None):
     tower_ms, screen_ms, finish_ms, refine_ms = rec["tower_ms"], rec["screen_ms"], rec["finish_ms"], rec["refine_ms"]
     scan_ms, select_ms, roofline, item_vec, out_r = (rec["scan_ms"], rec["select_ms"], rec["roofline"],
                                                       rec["item_vec"], rec["out_r"])
+    if args.dump_outputs and rank == 0:  # before any other leg runs the step again
+        sampled = dump_outputs(args.dump_outputs, rec["outputs"])
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {', '.join(rec['outputs'])}"
+            + ("" if sampled is None else f" ({len(sampled)} sampled users of {rec['outputs']['topk_rows'].shape[0]})"))
     # N > 1 with the users-sharded headline: BASELINE config 4 (the catalog
     # sharded over the same N ranks, strong scaling of one 250k-user problem,
     # the two RCCL exchanges) measured beside it

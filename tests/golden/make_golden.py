@@ -18,6 +18,10 @@ YoutubeDNN / YoutubeDNNRecaller.train/_extract_embeddings/recall, DINModel,
 DINDataset, collate_fn -- is the reference's own code, executed unchanged.
 
 Usage:  python tests/golden/make_golden.py   (writes *.npz next to this file)
+
+No committed file may exceed 1 MiB, so a fixture that would is written as
+parts (save_parts: <name>.0.npz, <name>.1.npz, ...), which the ``golden``
+fixture of tests/conftest.py puts together again, array for array.
 """
 from __future__ import annotations
 
@@ -67,6 +71,53 @@ class IndexFlatIP:
             D[qi, : len(order)] = s[order].astype(np.float32)
             I[qi, : len(order)] = order
         return D, I
+
+
+PART_BYTES = 800_000  # compressed bytes per part, well under the 1 MiB limit for a committed file
+
+
+def save_parts(path, **arrays):
+    """np.savez_compressed(path, **arrays) while the file stays under 1 MiB;
+    else parts of at most PART_BYTES, <name>.0.npz, <name>.1.npz, ...: "__keys__" in part 0
+    holds the keys in order, every part holds whole arrays, and an array too
+    large for one part is cut along axis 0 into pieces "<key>@@<i>of<n>" (the
+    loader concatenates them).  Lossless: same keys, order, dtypes, values."""
+    import io
+    import zlib
+
+    stem = path[:-len(".npz")]
+    for old in os.listdir(HERE):  # the other form of the same fixture
+        if old == os.path.basename(path) or (old.startswith(os.path.basename(stem) + ".") and old.endswith(".npz")):
+            os.remove(os.path.join(HERE, old))
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    if buf.tell() < 1 << 20:
+        with open(path, "wb") as fh:
+            fh.write(buf.getvalue())
+        return [path]
+    assert "__keys__" not in arrays and not any("@@" in k for k in arrays)
+    size = lambda a: len(zlib.compress(np.ascontiguousarray(a).tobytes(), 6)) + 512  # noqa: E731
+    items = []
+    for k, a in arrays.items():
+        n = -(-size(a) // (PART_BYTES // 2))  # pieces no larger than half a part
+        if n == 1 or a.ndim == 0:
+            items.append((k, a))
+        else:
+            items += [(f"{k}@@{i}of{n}", piece) for i, piece in enumerate(np.array_split(a, n, axis=0))]
+    parts, used = [{"__keys__": np.array(list(arrays))}], size(np.array(list(arrays)))
+    for k, a in items:
+        if used + size(a) > PART_BYTES:
+            parts.append({})
+            used = 0
+        parts[-1][k] = a
+        used += size(a)
+    out = []
+    for i, part in enumerate(parts):
+        out.append(f"{stem}.{i}.npz")
+        np.savez_compressed(out[-1], **part)
+        assert os.path.getsize(out[-1]) < 1 << 20, out[-1]
+    return out
 
 
 def import_reference():
@@ -176,7 +227,7 @@ def gen_itemcf(tmp):
             uts.append(ts)
         uoff.append(len(uitems))
     cids = np.array(sorted(created.keys()), dtype=np.int64)
-    np.savez_compressed(
+    save_parts(
         os.path.join(HERE, "itemcf_small.npz"),
         click_user=click_df["user_id"].to_numpy(np.int64),
         click_item=click_df["click_article_id"].to_numpy(np.int64),
@@ -248,7 +299,7 @@ def gen_youtubednn(tmp):
             rs.append(sc)
         roff.append(len(ri))
     n_items_enc = len(rec.item_index_2_rawid)
-    np.savez_compressed(
+    save_parts(
         os.path.join(HERE, "youtubednn_small.npz"),
         click_user=click_df["user_id"].to_numpy(np.int64),
         click_item=click_df["click_article_id"].to_numpy(np.int64),
@@ -347,7 +398,7 @@ def gen_topk(tmp):
     D, I = idx.search(users_a[:4], 16)
     out["small_D"], out["small_I"] = D, I
     out["k"] = np.int64(k)
-    np.savez_compressed(os.path.join(HERE, "topk_small.npz"), **out)
+    save_parts(os.path.join(HERE, "topk_small.npz"), **out)
     print("topk_small: sets a (random) and b (tie stress)")
 
 
@@ -378,7 +429,7 @@ def gen_embsim(tmp):
             si.append(i)
             sj.append(j)
             sv.append(v)
-    np.savez_compressed(
+    save_parts(
         os.path.join(HERE, "embsim_small.npz"),
         ids=ids, emb=emb, topk=np.int64(cfg.embedding_topk),
         sim_i=np.array(si, np.int64), sim_j=np.array(sj, np.int64), sim_v=np.array(sv, np.float64),
@@ -451,7 +502,7 @@ def gen_din(tmp):
     out["user_feats"] = np.array(USER_FEATS)
     out["item_feats"] = np.array(ITEM_FEATS)
     out["ctx_feats"] = np.array(CTX_FEATS)
-    np.savez_compressed(os.path.join(HERE, "din_small.npz"), **out)
+    save_parts(os.path.join(HERE, "din_small.npz"), **out)
     print("din_small: B in {512, 4096, 37}, T=50")
 
 
@@ -539,7 +590,7 @@ def gen_din_encode(tmp):
     }
     for f in USER_FEATS + ITEM_FEATS + CTX_FEATS:
         out[f"classes::{f}"] = np.array([str(c) for c in enc[f].classes_])
-    np.savez_compressed(os.path.join(HERE, "din_encode_small.npz"), **out)
+    save_parts(os.path.join(HERE, "din_encode_small.npz"), **out)
     print("din_encode_small: host encoding fixture")
 
 
@@ -660,7 +711,7 @@ def gen_rank_pipeline(tmp):
             out[f"{p}classes::{f}"] = c.astype(str) if c.dtype == object else c
     out["user_feats"], out["item_feats"], out["ctx_feats"] = (np.array(USER_FEATS), np.array(ITEM_FEATS),
                                                                np.array(CTX_FEATS))
-    np.savez_compressed(os.path.join(HERE, "rank_pipeline_small.npz"), **out)
+    save_parts(os.path.join(HERE, "rank_pipeline_small.npz"), **out)
     print("rank_pipeline_small: DINRanker.load/load_model/predict at D in {32, 16, 64}, bs 128 / 100")
 
 
@@ -726,7 +777,7 @@ def gen_fusion(tmp):
         tag = f"out::{strat}::{norm}::{int(seen)}"
         out[tag + "::users"], out[tag + "::offsets"], out[tag + "::items"], out[tag + "::scores"] = \
             _flat_dict(res)
-    np.savez_compressed(os.path.join(HERE, "fusion_small.npz"), **out)
+    save_parts(os.path.join(HERE, "fusion_small.npz"), **out)
 
 
 # --------------------------------------------------------------------------
@@ -837,7 +888,7 @@ def gen_ctxfeat(tmp):
             out[f"edges::{f}"] = np.asarray(fe.discretizers[f].bin_edges_[0], np.float64)
         out[f"classes::{f}"] = np.asarray(ns.label_encoders[f].classes_).astype(str)
     out["codes"] = codes
-    np.savez_compressed(os.path.join(HERE, "ctxfeat_small.npz"), **out)
+    save_parts(os.path.join(HERE, "ctxfeat_small.npz"), **out)
 
 
 def main():

@@ -7,7 +7,7 @@ rc=$?
 tail -15 "$out/pytest.log"
 if [ $rc -gt 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit $?
-timeout -k 10 400 python bench.py --steps 10 --warmup 3 > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 python bench.py --full --steps 10 --warmup 3 > "$out/bench.json" 2> "$out/bench.err"
 rc2=$?
 tail -3 "$out/bench.err"; cat "$out/bench.json"
 exit $(( rc > rc2 ? rc : rc2 ))

@@ -7,7 +7,7 @@ half of the bytes of wide coalesced reads, so it is doubled; WRITE_SIZE is
 taken as is.  Both include Infinity-Cache hits (memory-side L2 requests).
 
 usage: pmc_traffic.py RECALL_FETCH RECALL_WRITE DIN_FETCH DIN_WRITE OUT
-  RECALL_*: passes over `bench.py --steps 1 --warmup 0 --no-din --no-cpu-baseline`
+  RECALL_*: passes over `bench.py --full --steps 1 --warmup 0 --no-din --no-cpu-baseline`
   DIN_*:    passes over `tools/din_prof.py 2` (two DIN config-3 passes); the
             "din_pass" entry sums every launch dispatched by the LAST
             nrk_din_forward_segments call (after the previous pass's

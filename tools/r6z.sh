@@ -7,5 +7,5 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_din.py tests/test_rank_pipe
 tail -2 $o/pytest.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o run -- python3 tools/din_prof.py 2 > $o/prof.log 2>&1 || { tail $o/prof.log; exit 1; }
 grep -h 'absmax' $o/prof/run_kernel_stats.csv | cut -d, -f1-4
-timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-itemcf --no-plugins > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-itemcf --no-plugins > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
 grep -o '"ms_per_pass": [0-9.]*' $o/bench.json

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/${1:-reh}; mkdir -p $O
 for n in ${2:-2 3}; do
-  timeout -k 10 600 python -u bench.py --gpus $n --backend gloo --steps 2 --warmup 1 --no-cpu-baseline --no-plugins \
+  timeout -k 10 600 python -u bench.py --full --gpus $n --backend gloo --steps 2 --warmup 1 --no-cpu-baseline --no-plugins \
     --no-itemcf --din-steps 2 --din-warmup 1 > $O/bench_$n.log 2>&1 || { tail -30 $O/bench_$n.log; exit 1; }
   grep -v "^E2026\|^W2026" $O/bench_$n.log | tail -3 | cut -c1-900
 done
