@@ -275,6 +275,19 @@ __device__ __forceinline__ uint32_t add_if(uint32_t x, uint64_t m) {
     (void)co;
     return r;
 }
+// the same in place (x is source and destination: no copy of a live position)
+__device__ __forceinline__ void add_if_to(uint32_t& x, uint64_t m) {
+    uint64_t co;
+    asm("v_addc_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(x), "=s"(co) : "s"(m));
+    (void)co;
+}
+
+// x - (lane bit of m), in place
+__device__ __forceinline__ void sub_if_to(uint32_t& x, uint64_t m) {
+    uint64_t co;
+    asm("v_subb_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(x), "=s"(co) : "s"(m));
+    (void)co;
+}
 
 // Sorted (descending) register list: insert v (v = -inf inserts nothing).
 // new[i] = max(t[i], min(t[i-1], v)) -- independent per element.  The scan
@@ -327,6 +340,20 @@ __device__ __forceinline__ uint32_t first_set_block(const uint64_t (&am)[TB]) {
         });
         return bs;
     }
+}
+// first_set_block<8> as one statement (nothing is scheduled into the chain)
+__device__ __forceinline__ uint32_t first_set_block8(const uint64_t (&am)[8]) {
+    uint32_t bs;
+    asm("v_cndmask_b32_e64 %0, 7, 6, %7\n\t"
+        "v_cndmask_b32_e64 %0, %0, 5, %6\n\t"
+        "v_cndmask_b32_e64 %0, %0, 4, %5\n\t"
+        "v_cndmask_b32_e64 %0, %0, 3, %4\n\t"
+        "v_cndmask_b32_e64 %0, %0, 2, %3\n\t"
+        "v_cndmask_b32_e64 %0, %0, 1, %2\n\t"
+        "v_cndmask_b32_e64 %0, %0, 0, %1"
+        : "=&v"(bs)
+        : "s"(am[0]), "s"(am[1]), "s"(am[2]), "s"(am[3]), "s"(am[4]), "s"(am[5]), "s"(am[6]));
+    return bs;
 }
 #if NRK_SCAN_STAMP
 __device__ unsigned long long scan_stamps[1024 * 16];
@@ -936,7 +963,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
 // later and do the appends and list inserts, so the matrix pipe never waits
 // for bookkeeping and an append store never gates a barrier.  One barrier per
 // step of TPS = 2 tiles (the MFMA waves pipeline both tiles as one block
-// sequence); main-pass inserts every insp tiles (the largest tile maximum
+// sequence, the book waves book a main-pass step's 8 blocks as one unit:
+// one store, one count per group and step); main-pass inserts every insp tiles (the largest tile maximum
 // since the last insert: the list stays a set of distinct appended
 // half-block maxima, so its (jk + 1)-th largest stays a lower bound; only tau
 // lags), pre-pass tiles every tile.  LDS: the 4-tile ring (32 KB) + 2 TPS
@@ -1231,15 +1259,17 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
 #pragma unroll
         for (int i = 0; i < MT; ++i) t[g][i] = (live[g] && i >= MT - 1 - jk) ? -INFINITY : INFINITY;
     }
+    // Appends: cnt[g] counts the entries offered to the lane's list of group g;
+    // entry e goes to slot min(e, m2 - 1) of the m2 slots at off0 (bytes) of
+    // the group's 64 lists.
     uint2* const wapp = app + (size_t)(ubase + gb * 32) * 2 * (size_t)m2;
-    const uint32_t pos0 = (uint32_t)(q * 2 + h) * (uint32_t)m2;  // group 0's first slot
-    const uint32_t gstride = 64u * (uint32_t)m2;                  // + g * gstride for group g
-    uint32_t pos[UGB];
+    const uint32_t off0 = ((uint32_t)(q * 2 + h) * (uint32_t)m2) << 3;
+    const size_t gstride = 64u * (size_t)m2;  // + g * gstride for group g
+    uint32_t cnt[UGB];
 #pragma unroll
-    for (int g = 0; g < UGB; ++g) pos[g] = pos0 + (uint32_t)g * gstride;
-    auto slot = [&](uint32_t x, int g) { return min(x, pos0 + (uint32_t)g * gstride + (uint32_t)m2 - 1u); };
-    auto app_store_if = [&](uint64_t m, uint32_t e, uint2 v) {
-        const uint32_t off = e << 3;
+    for (int g = 0; g < UGB; ++g) cnt[g] = 0u;
+    auto app_store_if = [&](uint64_t m, int g, uint32_t e, uint2 v) {
+        const uint32_t off = (min(e, (uint32_t)m2 - 1u) << 3) + off0;
         const uint64_t d = ((uint64_t)v.y << 32) | v.x;
         uint64_t sv;
         asm volatile(
@@ -1247,7 +1277,7 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
             "global_store_dwordx2 %2, %3, %4\n\t"
             "s_mov_b64 exec, %0"
             : "=&s"(sv)
-            : "s"(m), "v"(off), "v"(d), "s"(wapp)
+            : "s"(m), "v"(off), "v"(d), "s"(wapp + (size_t)g * gstride)
             : "memory", "scc");
     };
     auto retau = [&](int g) {
@@ -1283,128 +1313,235 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
                 : "memory");
         }
     };
-    // tile t's reads landed with `left' later reads still in flight (LDS
-    // reads return in order: left = 0 or the reads of one more tile, TPS <= 2);
-    // the wait ties rr[t], so nothing copies it earlier
-    static_assert(TPS <= 2, "read_wait");
-    auto read_wait = [&](int t, bool left) {
-        constexpr int L1 = TB * (UGB / 4);
+    // tile t's reads landed with LEFT later reads still in flight (LDS reads
+    // return in order, and every step issues the reads of all its TPS tiles,
+    // so LEFT is a constant of the call site); the wait ties rr[t], so nothing
+    // uses it earlier.  The reads define rr unconditionally and the ties keep
+    // it in place: no register copy between a read and its use.
+    auto read_wait = [&](int t, auto left_c) __attribute__((always_inline)) {
+        constexpr int LEFT = decltype(left_c)::value;
+        auto& r = rr[t];
         if constexpr (NB == 2) {
-            if (left)
-                asm volatile("s_waitcnt lgkmcnt(%4)"
-                             : "+v"(rr[t][0][0]), "+v"(rr[t][1][0]), "+v"(rr[t][2][0]), "+v"(rr[t][3][0])
-                             : "n"(L1)
-                             : "memory");
-            else
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(rr[t][0][0]), "+v"(rr[t][1][0]), "+v"(rr[t][2][0]), "+v"(rr[t][3][0])::"memory");
+            asm volatile("s_waitcnt lgkmcnt(%4)"
+                         : "+v"(r[0][0]), "+v"(r[1][0]), "+v"(r[2][0]), "+v"(r[3][0])
+                         : "n"(LEFT)
+                         : "memory");
         } else {
-            if (left)
-                asm volatile("s_waitcnt lgkmcnt(%8)"
-                             : "+v"(rr[t][0][0]), "+v"(rr[t][0][1]), "+v"(rr[t][1][0]), "+v"(rr[t][1][1]),
-                               "+v"(rr[t][2][0]), "+v"(rr[t][2][1]), "+v"(rr[t][3][0]), "+v"(rr[t][3][1])
-                             : "n"(L1)
-                             : "memory");
-            else
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(rr[t][0][0]), "+v"(rr[t][0][1]), "+v"(rr[t][1][0]), "+v"(rr[t][1][1]),
-                               "+v"(rr[t][2][0]), "+v"(rr[t][2][1]), "+v"(rr[t][3][0]), "+v"(rr[t][3][1])::"memory");
+            asm volatile("s_waitcnt lgkmcnt(%8)"
+                         : "+v"(r[0][0]), "+v"(r[0][1]), "+v"(r[1][0]), "+v"(r[1][1]), "+v"(r[2][0]), "+v"(r[2][1]),
+                           "+v"(r[3][0]), "+v"(r[3][1])
+                         : "n"(LEFT)
+                         : "memory");
         }
     };
+    // The appends of the NBK = TPS TB consecutive blocks of a step for group g:
+    // every half-block maximum >= tau is one entry (value, half-block id), in
+    // block order; hb = the first block's id.  A lane with one passing block
+    // -- the common case -- stores (the maximum of the NBK blocks, which is
+    // that block's; the first passing block's id) in one masked store for the
+    // whole group; a lane that passes twice redoes its entries from the same
+    // slot (below).  Either way a lane's list gets the entries a walk block by
+    // block gives it, so every (user, half) list holds the same entries in the
+    // same order, and acnt is the same, as when each tile is booked on its
+    // own: tau is constant over a step (inserts and retau fall after a step's
+    // last tile: insp is a power of two >= TPS).
+    auto append = [&](auto gc, const auto& mx, float vmx, uint32_t hb) __attribute__((always_inline)) {
+        constexpr int g = decltype(gc)::value;
+        constexpr int NBK = (int)std::extent_v<std::remove_reference_t<decltype(mx)>>;
+        uint64_t am[NBK], gm = 0, multi = 0;
+#pragma unroll
+        for (int b = 0; b < NBK; ++b) {
+            am[b] = __builtin_amdgcn_ballot_w64(mx[b] >= tau[g]);
+            multi |= gm & am[b];
+            gm |= am[b];
+        }
+        if (gm) {
+            uint32_t bs;
+            if constexpr (NBK == 8) bs = first_set_block8(am);
+            else bs = first_set_block<NBK>(am);
+            app_store_if(gm, g, cnt[g], make_uint2(__float_as_uint(vmx), (bs << 1) + hb));
+            add_if_to(cnt[g], gm);
+            if (__builtin_expect(multi != 0, 0)) {
+                // The lanes that pass twice, again from the same slot.  Two
+                // passes in one step are mostly one in each tile (with 64
+                // lanes about one group step in twelve has such a lane), so
+                // they go tile by tile in the same form -- one store of (tile
+                // maximum, first passing block of the tile) -- and block by
+                // block only for a lane that passes twice in one tile.
+                sub_if_to(cnt[g], multi);
+                static_for<NBK / TB>([&](auto tc) {
+                    constexpr int B0 = decltype(tc)::value * TB;
+                    uint64_t at[TB], gt = 0, mt = 0;
+#pragma unroll
+                    for (int b = 0; b < TB; ++b) {
+                        at[b] = am[B0 + b] & multi;
+                        mt |= gt & at[b];
+                        gt |= at[b];
+                    }
+                    if (gt) {
+                        const float vt = fmaxf(fmaxf(mx[B0], mx[B0 + 1]), fmaxf(mx[B0 + 2], mx[B0 + 3]));
+                        const uint32_t ft = (first_set_block<TB>(at) << 1) + hb + 2u * B0;
+                        app_store_if(gt, g, cnt[g], make_uint2(__float_as_uint(vt), ft));
+                        add_if_to(cnt[g], gt);
+                        if (mt) {
+                            sub_if_to(cnt[g], mt);
+#pragma unroll
+                            for (int b = 0; b < TB; ++b) {
+                                app_store_if(at[b] & mt, g, cnt[g],
+                                             make_uint2(__float_as_uint(mx[B0 + b]), hb + 2u * (B0 + b)));
+                                add_if_to(cnt[g], at[b] & mt);
+                            }
+                        }
+                    }
+                });
+            }
+        }
+    };
+    auto step_reads = [&](int p1) {  // the maxima of step p1's TPS tiles (a tile past nseq: an existing slot)
+#pragma unroll
+        for (int t = 0; t < TPS; ++t) read_issue(t, mq + (uint32_t)(((p1 & 1) * TPS + t) * MXS));
+    };
+    // a pre-pass tile: no appends, one insert per tile (they fill the list)
+    auto pre_tile = [&](auto tc) __attribute__((always_inline)) {
+        constexpr int T = decltype(tc)::value;
+#pragma unroll
+        for (int g = 0; g < UGB; ++g) {
+            const auto& r = rr[T];
+            const float vt = fmaxf(fmaxf(r[0][g / 4][g % 4], r[1][g / 4][g % 4]),
+                                   fmaxf(r[2][g / 4][g % 4], r[3][g / 4][g % 4]));
+            const bool in = vt > t[g][MT - 1];
+            if (__builtin_amdgcn_ballot_w64(in)) top_insert<MT>(t[g], in ? vt : -INFINITY);
+        }
+    };
+    constexpr int L1 = TB * (UGB / 4);  // maxima reads per tile
     // main-pass inserts every insp tiles (a power of two >= TPS; the host's
     // choice, see launch_scan_v)
-    float vtp[UGB];  // INSP > 1: the largest tile maximum since the last insert, per group (-inf: none)
+    float vtp[UGB];  // the largest tile maximum since the last insert, per group (-inf: none)
 #pragma unroll
     for (int g = 0; g < UGB; ++g) vtp[g] = -INFINITY;
-    for (int p = 0; p <= NP; ++p) {
+    SC_STAMP(5);
+    sync();  // step 0's maxima are under way: nothing to book yet
+    SC_STAMP(0);
+    // Steps of pre-pass tiles only.
+    const int PA = n_pre / TPS;
+    for (int p1 = 0; p1 < PA; ++p1) {
         SC_STAMP(5);
         sync();
         SC_STAMP(0);
-        if (p == 0) continue;
-        const int p1 = p - 1;
-#pragma unroll
-        for (int t = 0; t < TPS; ++t)
-            if (TPS * p1 + t < nseq) read_issue(t, mq + (uint32_t)(((p1 & 1) * TPS + t) * MXS));
+        step_reads(p1);
+#if NRK_SCAN_WS_FLOOR  // dev timing floor: the book waves only read the maxima
+        read_wait(TPS - 1, std::integral_constant<int, 0>{});
+        if (rr[TPS - 1][0][0][0] != 12345.0f) continue;
+#endif
         static_for<TPS>([&](auto tc) {
-        constexpr int T = decltype(tc)::value;
-        const int j = TPS * p1 + T;
-        if (j >= nseq) return;
-        read_wait(T, T + 1 < TPS && j + 1 < nseq);  // tile T + 1's reads may stay in flight
-        const int tt = seq(j);
-        const bool pre = j < n_pre;
-        if (j == n_pre) {  // the first main-pass tile: tau from the pre-pass lists
+            constexpr int T = decltype(tc)::value;
+            read_wait(T, std::integral_constant<int, (TPS - 1 - T) * L1>{});  // later tiles' reads stay in flight
+            SC_STAMP(1);
+            pre_tile(tc);
+            SC_STAMP(4);
+        });
+    }
+    // Every later step is booked as one unit of TPS TB consecutive main-pass
+    // blocks: per group one maximum, one masked store, one count and one vtp
+    // update (see append).  Tiles of such a step that are not main-pass tiles
+    // count as -inf, which passes no tau and changes no maximum: the pre-pass
+    // tiles in front of the first main-pass tile when TPS does not divide
+    // n_pre (they are booked as pre-pass tiles first), and the tiles past
+    // nseq of a short last step.
+    for (int p1 = PA; p1 < NP; ++p1) {
+        SC_STAMP(5);
+        sync();
+        SC_STAMP(0);
+        step_reads(p1);
+        const int j0 = TPS * p1;
+        static_for<TPS>([&](auto tc) { read_wait(decltype(tc)::value, std::integral_constant<int, 0>{}); });
+        SC_STAMP(1);
+#if NRK_SCAN_WS_FLOOR
+        if (rr[TPS - 1][0][0][0] != 12345.0f) continue;
+#endif
+        if (p1 == PA) {  // the first main-pass tile is in this step: tau from the pre-pass lists
+            static_for<TPS>([&](auto tc) {
+                constexpr int T = decltype(tc)::value;
+                if (j0 + T < n_pre) {
+                    pre_tile(tc);
+#pragma unroll
+                    for (int b = 0; b < TB; ++b)
+#pragma unroll
+                        for (int c = 0; c < UGB / 4; ++c)
+                            rr[T][b][c] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                }
+            });
 #pragma unroll
             for (int g = 0; g < UGB; ++g) retau(g);
         }
-        bool ins_ok = true;
-        if (!pre && tt == next_s) {  // a sampled tile: its maxima are in the lists already
-            ins_ok = false;
-            next_s = --left_s > 0 ? next_s + pstride : INT_MAX;
+        const bool whole = j0 + TPS <= nseq;
+        if (!whole) {  // a short last step
+            static_for<TPS>([&](auto tc) {
+                constexpr int T = decltype(tc)::value;
+                if (j0 + T >= nseq) {
+#pragma unroll
+                    for (int b = 0; b < TB; ++b)
+#pragma unroll
+                        for (int c = 0; c < UGB / 4; ++c)
+                            rr[T][b][c] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                }
+            });
         }
-        const auto& r = rr[T];
-        SC_STAMP(1);
-#if NRK_SCAN_WS_FLOOR  // dev timing floor: the book waves only read the maxima
-        if (r[0][0][0] != 12345.0f) return;
-#endif
-        const uint32_t hb0 = (uint32_t)(tt * TB * 2) + (uint32_t)h;
-        // group g of the tile
+        // the step's tiles are tt0 .. tt0 + TPS - 1 (consecutive in the main
+        // pass; for a tile in front of the first main-pass tile the number is
+        // formal)
+        const int tt0 = seq(j0 + TPS - 1) - (TPS - 1);
+        // sampled tiles: their maxima are in the lists already, so they append
+        // as usual and count as -inf for the inserts
+        bool smp[TPS], any_smp = false;
+#pragma unroll
+        for (int t = 0; t < TPS; ++t) {
+            smp[t] = tt0 + t == next_s;
+            if (smp[t]) {
+                any_smp = true;
+                next_s = --left_s > 0 ? next_s + pstride : INT_MAX;
+            }
+        }
+        uint32_t hb0 = (uint32_t)(tt0 * TB * 2) + (uint32_t)h;
+        asm volatile("" : "+v"(hb0));  // formed once per step, not per group
         static_for<UGB>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
-            float mx[TB];
+            constexpr int NBK = TPS * TB;
+            float mx[NBK];
 #pragma unroll
-            for (int b = 0; b < TB; ++b) mx[b] = r[b][g / 4][g % 4];
-            const float vt = fmaxf(fmaxf(mx[0], mx[1]), fmaxf(mx[2], mx[3]));
-            if (!pre) {
-                // appends (ip_scan_seg's BSEL form): every half-block max >= tau
-                uint64_t am[TB], gm = 0, multi = 0;
+            for (int b = 0; b < NBK; ++b) mx[b] = rr[b / TB][b % TB][g / 4][g % 4];
+            float v = mx[0];
 #pragma unroll
-                for (int b = 0; b < TB; ++b) {
-                    am[b] = __builtin_amdgcn_ballot_w64(mx[b] >= tau[g]);
-                    multi |= gm & am[b];
-                    gm |= am[b];
-                }
-                if (gm) {
-                    const uint32_t fid = (first_set_block<TB>(am) << 1) + hb0;
-                    const uint32_t p0 = pos[g];
-                    app_store_if(gm, slot(p0, g), make_uint2(__float_as_uint(vt), fid));
-                    uint32_t p = add_if(p0, gm);
-                    if (multi) {
-                        p = p0;
-#pragma unroll
-                        for (int b = 0; b < TB; ++b) {
-                            app_store_if(am[b] & multi, slot(p, g), make_uint2(__float_as_uint(mx[b]), hb0 + 2u * b));
-                            p = add_if(p, am[b]);
-                        }
-                    }
-                    pos[g] = p;
-                }
-            }
+            for (int b = 1; b + 1 < NBK; b += 2) v = fmaxf(fmaxf(v, mx[b]), mx[b + 1]);
+            if constexpr (NBK % 2 == 0) v = fmaxf(v, mx[NBK - 1]);
+            append(gc, mx, v, hb0);
             SC_STAMP(2);
-            if (pre) {
-                // pre-pass tiles insert every tile (they fill the list)
-                const bool in = vt > t[g][MT - 1];
-                if (__builtin_amdgcn_ballot_w64(in)) top_insert<MT>(t[g], in ? vt : -INFINITY);
-            } else {
-                // main pass: one insert per INSP tiles, the largest of their
-                // tile maxima (a sampled tile's counts as -inf); the list stays
-                // a set of distinct appended half-block maxima, so its (jk +
-                // 1)-th largest stays a lower bound -- only tau lags by < INSP
-                // tiles
-                const float vi = fmaxf(ins_ok ? vt : -INFINITY, vtp[g]);
-                if (T + 1 < TPS || ((j - n_pre) & (insp - 1)) < insp - TPS) {
-                    vtp[g] = vi;
-                } else {
-                    vtp[g] = -INFINITY;
-                    const bool in = vi > t[g][MT - 1];
-                    if (__builtin_amdgcn_ballot_w64(in)) {
-                        top_insert<MT>(t[g], in ? vi : -INFINITY);
-                        if (!pre) retau(g);
-                    }
+            float vins = v;
+            if (__builtin_expect(any_smp, 0)) {
+                vins = -INFINITY;
+#pragma unroll
+                for (int b = 0; b < NBK; ++b)
+                    if (!smp[b / TB]) vins = fmaxf(vins, mx[b]);
+            }
+            vtp[g] = fmaxf(vins, vtp[g]);
+        });
+        // One insert per insp tiles, the largest of their tile maxima, when
+        // the step's last tile ends an insert period.  The list stays a set of
+        // distinct appended half-block maxima, so its (jk + 1)-th largest
+        // stays a lower bound -- only tau lags by < insp tiles.
+        if (whole && ((j0 + TPS - 1 - n_pre) & (insp - 1)) >= insp - TPS) {
+#pragma unroll
+            for (int g = 0; g < UGB; ++g) {
+                const float vi = vtp[g];
+                vtp[g] = -INFINITY;
+                const bool in = vi > t[g][MT - 1];
+                if (__builtin_amdgcn_ballot_w64(in)) {
+                    top_insert<MT>(t[g], in ? vi : -INFINITY);
+                    retau(g);
                 }
             }
-            SC_STAMP(4);
-        });
-        });
+        }
+        SC_STAMP(4);
     }
     {  // the maxima since the last insert
 #pragma unroll
@@ -1423,7 +1560,7 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
         const float lb = pair_min32(t[g][MT - 1]);
         const int user = ubase + (gb + g) * 32 + q;
         if (user < n_users) {
-            acnt[(size_t)user * 2 + h] = (int)(pos[g] - (pos0 + (uint32_t)g * gstride));
+            acnt[(size_t)user * 2 + h] = (int)cnt[g];
             if (h == 0) reinterpret_cast<float*>(uinfo + user)[0] = live[g] ? lb : -INFINITY;
         }
     }
