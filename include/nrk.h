@@ -302,6 +302,72 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
                       int32_t* out_cnt, void* workspace, size_t workspace_bytes, nrk_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* UserCF user-to-user similarity and recall                              */
+/* ---------------------------------------------------------------------- */
+
+/* Replaces UserCFSimilarity.calculate (src/similarity/user_cf.py:31-66),
+ * which the reference ships but comments out of its pipeline
+ * (src/recall/recall_pipeline.py:137,151-155): its host loop is
+ * O(sum_items n_i^2) and stores every user pair.  Dense user and item ids.
+ *   i_off [n_items + 1], i_users [n_clicks]: the item -> user CSR, items in
+ *     ascending raw id, entries in the order of
+ *     InteractionFeatureExtractor.get_item_user_time_dict
+ *     (src/data/extractors.py:200-231);
+ *   u_off [n_users + 1], u_items [n_clicks]: every user's clicks sorted by
+ *     item, duplicates kept;
+ *   act [n_users] the activate degree, pen [n_items] = 1.0 / log(n_i + 1),
+ *     both fp64, formed on the host.
+ * Row u's value for v is the fp64 sum of (50.0 * (act[u] + act[v])) * pen[i]
+ * over the reference's (item, u entry, v entry) order, divided by
+ * sqrt(cnt[u] * cnt[v]) -- bit-identical to the reference -- and its first
+ * slot is the smallest index into i_users at which v stands in an item that
+ * u clicked (the reference's dict insertion order).
+ * nrk_usercf_topn: per user the top-n by (value desc, first slot asc), the
+ * reference's stable sorted(..., reverse=True)[:topn]: out_cols / out_vals
+ * [n_users, topn] (-1 / 0 padded), out_cnt [n_users] click rows, out_nnz
+ * [n_users] distinct neighbours.  The u2u matrix is never materialised: the
+ * workspace holds a fixed number of dense rows.  topn <= 1024.
+ * nrk_usercf_sim: every (v, value, first slot) of every row, row u at
+ * row_off[u] (row_off = the exclusive scan of out_nnz, n_entries its total),
+ * entries of a row in no particular order (sort by first slot).  Same
+ * workspace. */
+size_t nrk_usercf_workspace_bytes(int64_t n_users, int64_t n_clicks, int topn);
+int nrk_usercf_topn(const int64_t* i_off, int32_t n_items, const int32_t* i_users, const int64_t* u_off,
+                    int64_t n_users, const int32_t* u_items, int64_t n_clicks, const double* act, const double* pen,
+                    int topn, int32_t* out_cols, double* out_vals, int64_t* out_cnt, int32_t* out_nnz,
+                    void* workspace, size_t workspace_bytes, nrk_stream_t stream);
+int nrk_usercf_sim(const int64_t* i_off, int32_t n_items, const int32_t* i_users, const int64_t* u_off,
+                   int64_t n_users, const int32_t* u_items, int64_t n_clicks, const double* act, const double* pen,
+                   const int64_t* row_off, int64_t n_entries, int32_t* out_v, double* out_s, int64_t* out_first,
+                   void* workspace, size_t workspace_bytes, nrk_stream_t stream);
+
+/* UserCFRecaller.recall (src/recall/usercf_recaller.py:37-118) for a batch of
+ * query users.  offsets / items: the user click lists in history order
+ * (user_item_time_dict), dense ids; q_slot[q] = the query's row or -1 (cold
+ * start, :48-53).  nbr_* [n_users, topn]: per user its top-n neighbours
+ * (dense user rows, nrk_usercf_topn's order); loc_w [n_users] = 1 + sum_loc
+ * beta^(L - loc) (:84-86), formed on the host.  Every click i of a
+ * neighbour, in (neighbour rank, history position) order and not in the
+ * query's history H, adds ((loc_w * content_w) * created_w) * w_uv with
+ * content_w = 1 + the emb_* entries of (i, j) and (j, i) and created_w = 1 +
+ * sum exp(created_alpha ^ |created_i - created_j|) over j in H (:76-102; the
+ * reference passes the literal 0.8).  The per-item sums in walk order, the
+ * hot fill and the top-k are those of nrk_itemcf_recall, and so are emb_*,
+ * hot, cand_off / n_cand (pass 1: nrk_usercf_recall_offsets), the outputs
+ * and the limits. */
+int nrk_usercf_recall_offsets(const int64_t* q_slot, int64_t n_query, const int64_t* offsets,
+                              const int32_t* nbr_cols, const int32_t* nbr_cnt, int topn, int64_t* cand_off,
+                              nrk_stream_t stream);
+size_t nrk_usercf_recall_workspace_bytes(int64_t n_cand);
+int nrk_usercf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* offsets, const int32_t* items,
+                      const int32_t* nbr_cols, const double* nbr_vals, const int32_t* nbr_cnt, int topn,
+                      const double* loc_w, const double* created, int32_t n_items, const int32_t* hot, int n_hot,
+                      const int32_t* emb_cols, const double* emb_vals, const int32_t* emb_cnt, int ke,
+                      double created_alpha, const int64_t* cand_off, int64_t n_cand, int topk, int32_t* out_items,
+                      double* out_scores, int32_t* out_src, int32_t* out_cnt, void* workspace,
+                      size_t workspace_bytes, nrk_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* DIN attention-over-history scorer                                      */
 /* ---------------------------------------------------------------------- */
 

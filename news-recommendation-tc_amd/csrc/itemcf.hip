@@ -24,6 +24,7 @@
 //                      insertion order, the reference's stable-sort tie-break).
 // Memory-bound integer/byte work: no MFMA; tiles of 4096 keys per 256-thread
 // workgroup, coalesced 16-element strips.
+#include "itemcf_backend.h"
 #include "nrk_common.h"
 
 #include <climits>
@@ -150,12 +151,7 @@ struct CfParams {
 // e^y |y| 2^-52 <= 2^-52 / e relative: below half an ulp of the factor (the
 // ItemCF bar is rtol 1e-12; device and host libm already differ by an ulp).
 // ln is NaN (-> the device pow) unless alpha is positive and finite.
-static inline double cf_ln(double alpha) {
-    return alpha > 0.0 && std::isfinite(alpha) ? std::log(alpha) : NAN;
-}
-__device__ __forceinline__ double cf_apow(double alpha, double ln_alpha, double x) {
-    return ln_alpha == ln_alpha ? exp(x * ln_alpha) : pow(alpha, x);
-}
+// (cf_ln / cf_apow: itemcf_backend.h, shared with usercf.hip)
 
 static inline int64_t cf_dt_zero(double time_alpha) {
     if (!(time_alpha > 0.0 && time_alpha < 1.0)) return INT64_MAX;
@@ -1933,19 +1929,55 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
                 "null pointer");
     NRK_REQUIRE(n_hot == 0 || hot, "hot is null");
     NRK_REQUIRE(ke == 0 || (emb_cols && emb_vals && emb_cnt), "emb arrays null");
-    const RcWs w = rc_ws_layout(workspace, n_cand);
-    NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
+    NRK_REQUIRE(workspace_bytes >= rc_back_bytes(n_cand), "workspace too small");
     hipStream_t s = as_stream(stream);
+    RcBack bk;
+    if (!rc_back_buffers(workspace, n_query, n_items, n_cand, &bk))
+        NRK_UNSUPPORTED("n_query * n_items too large for 64-bit keys");
+    const int64_t g = (n_query + 3) / 4;
+    const int gq = (int)(g < 65536 ? g : 65536);
+    const RcParams prm{loc_beta, created_alpha, cf_ln(created_alpha), topn, ke, bk.bj};
+    if (n_cand > 0)
+        rc_cand_kernel<<<gq, 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created,
+                                          emb_cols, emb_vals, emb_cnt, prm, cand_off, bk.sentinel, bk.keys,
+                                          bk.slots, bk.contrib);
+    return rc_back_finish(q_slot, n_query, offsets, items, n_items, hot, n_hot, cand_off, n_cand, topk, out_items,
+                          out_scores, out_src, out_cnt, workspace, s);
+}
+
+}  // extern "C"
+
+namespace nrk {
+
+size_t rc_back_bytes(int64_t n_cand) { return rc_ws_layout(nullptr, n_cand).bytes; }
+
+bool rc_back_buffers(void* workspace, int64_t n_query, int32_t n_items, int64_t n_cand, RcBack* out) {
+    const RcWs w = rc_ws_layout(workspace, n_cand);
     const int bj = bits_for(n_items);
-    const int bq = bits_for(n_query);
-    const int nbits = bj + bq;
-    if (nbits > 64) NRK_UNSUPPORTED("n_query * n_items too large for 64-bit keys");
+    const int nbits = bj + bits_for(n_query);
+    if (nbits > 64) return false;
+    *out = RcBack{w.sort.ka, w.sort.va, w.sort.w, (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1), bj};
+    return true;
+}
+
+void rc_scan_exclusive(int64_t* v, int64_t n, hipStream_t s) {
+    scan_exclusive_kernel<ScanVals><<<1, 1024, 0, s>>>(ScanVals{v}, n, v);
+}
+
+// The recall after its candidates are written (rc_cand_kernel for ItemCF,
+// uc_cand_kernel of usercf.hip for UserCF).
+int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offsets, const int32_t* items,
+                   int32_t n_items, const int32_t* hot, int n_hot, const int64_t* cand_off, int64_t n_cand, int topk,
+                   int32_t* out_items, double* out_scores, int32_t* out_src, int32_t* out_cnt, void* workspace,
+                   hipStream_t s) {
+    const RcWs w = rc_ws_layout(workspace, n_cand);
+    const int bj = bits_for(n_items);
+    const int nbits = bj + bits_for(n_query);
     const uint64_t sentinel = (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1);
     const int64_t g = (n_query + 3) / 4;
     const int gq = (int)(g < 65536 ? g : 65536);
     const int64_t n = n_cand;
     const int nblk = (int)((n + RS_TILE - 1) / RS_TILE);
-    const RcParams prm{loc_beta, created_alpha, cf_ln(created_alpha), topn, ke, bj};
     // topk <= 64: every query with <= RC_CAP candidates is finished by
     // rc_query_kernel from rc_cand's output; the radix path then runs over
     // the listed larger queries only, compacted to the front of the sort
@@ -1955,9 +1987,6 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
     const int64_t* n_dev = nullptr;
     int gl = gq;
     if (n > 0) {
-        rc_cand_kernel<<<gq, 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created,
-                                          emb_cols, emb_vals, emb_cnt, prm, cand_off, sentinel, w.sort.ka,
-                                          w.sort.va, w.sort.w);
         uint64_t* kin = w.sort.ka;
         uint64_t* kout = w.sort.kb;
         int32_t* vin = w.sort.va;
@@ -2025,6 +2054,10 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
+
+}  // namespace nrk
+
+extern "C" {
 
 int nrk_itemcf_row_offsets(const int32_t* ei, int64_t n, int64_t n_rows, int64_t* row_off, nrk_stream_t stream) {
     clear_error();

@@ -66,6 +66,13 @@ SIGNATURES = {
     "nrk_itemcf_recall_workspace_bytes": (SZ, [I64]),
     "nrk_itemcf_recall": (INT, [P, I64, P, P, P, P, P, INT, P, I32, P, INT, P, P, P, INT, F64, F64, P, I64,
                                 INT, P, P, P, P, P, SZ, P]),
+    "nrk_usercf_workspace_bytes": (SZ, [I64, I64, INT]),
+    "nrk_usercf_topn": (INT, [P, I32, P, P, I64, P, I64, P, P, INT, P, P, P, P, P, SZ, P]),
+    "nrk_usercf_sim": (INT, [P, I32, P, P, I64, P, I64, P, P, P, I64, P, P, P, P, SZ, P]),
+    "nrk_usercf_recall_offsets": (INT, [P, I64, P, P, P, INT, P, P]),
+    "nrk_usercf_recall_workspace_bytes": (SZ, [I64]),
+    "nrk_usercf_recall": (INT, [P, I64, P, P, P, P, P, INT, P, P, I32, P, INT, P, P, P, INT, F64, P, I64,
+                                INT, P, P, P, P, P, SZ, P]),
     "nrk_din_assemble": (INT, [P, P, I64, INT, INT, INT, P, INT, P, I64, INT, P, P, INT, INT, INT,
                                ctypes.c_float, ctypes.c_float, ctypes.c_uint32, I64, I64, P, P, P, P, P, P, P]),
     "nrk_gather_rows": (INT, [P, I64, INT, P, I64, P, P]),

@@ -18,6 +18,8 @@ class RecallConfig:
     itemcf_sim_item_topk: int = 20
     itemcf_recall_num: int = 20
     itemcf_hot_topk: int = 20
+    usercf_sim_user_topk: int = 20
+    usercf_recall_num: int = 10
     embedding_topk: int = 20
     embedding_dim: int = 64
     youtubednn_seq_max_len: int = 30

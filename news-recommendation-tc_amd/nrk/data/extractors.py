@@ -35,6 +35,41 @@ def csr_to_dict(users, offsets, items, ts):
             for n, u in enumerate(users)}
 
 
+def item_user_time_csr(click_df):
+    """-> (raw item ids [I] asc, offsets [I+1], raw user ids [N], ts [N]):
+    InteractionFeatureExtractor.get_item_user_time_dict (extractors.py:200-231)
+    in array form -- the same unstable ``sort_values("click_timestamp")`` call
+    (see the note on ``user_item_time_csr``), then ``groupby("click_article_id")``:
+    ascending item ids, group rows in sorted-frame order."""
+    df = click_df.sort_values("click_timestamp")
+    it = df["click_article_id"].to_numpy()
+    order = np.argsort(it, kind="stable")
+    it = it[order]
+    users = df["user_id"].to_numpy()[order]
+    ts = df["click_timestamp"].to_numpy()[order]
+    items, starts = np.unique(it, return_index=True)
+    offsets = np.append(starts, len(it)).astype(np.int64)
+    return items.astype(np.int64), offsets, users.astype(np.int64), ts.astype(np.int64)
+
+
+def user_activate_degree(click_df):
+    """{user_id: MinMax-scaled click count} == UserFeatureExtractor.
+    get_user_activate_degree_dict (extractors.py:39-62); sklearn's MinMaxScaler
+    arithmetic written out (``X * scale_ + min_`` in float64), as
+    synth.minmax_created does."""
+    users, counts = np.unique(click_df["user_id"].to_numpy(), return_counts=True)
+    x = counts.astype(np.float64)
+    if not len(x):
+        return {}
+    lo, hi = x.min(), x.max()
+    rng_ = hi - lo
+    scale = 1.0 / (rng_ if rng_ != 0 else 1.0)
+    min_ = 0.0 - lo * scale
+    out = x * scale
+    out += min_
+    return dict(zip(users.tolist(), out.tolist()))
+
+
 def item_created_time(item_info_df):
     """{item_id: MinMax-scaled created_at_ts} (extractors.py:149-163)."""
     from sklearn.preprocessing import MinMaxScaler

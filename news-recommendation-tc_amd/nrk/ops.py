@@ -697,6 +697,155 @@ def itemcf_recall(q_slot, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created, 
     return oi, osc, osrc, ocnt
 
 
+# ----------------------------------------------------------------- usercf --
+UC_TOPN_MAX = 1024  # nrk_usercf_topn's LDS selection
+
+
+def _csr_ok(off, idx, n_cols, what):
+    """offsets non-decreasing from 0 to len(idx), ids in [0, n_cols): on the
+    device an id out of range is an out-of-bounds access."""
+    if off.dim() != 1 or off.numel() < 1:
+        raise ValueError(f"{what} offsets must be 1-D with rows + 1 entries")
+    if int(off[0]) != 0 or int(off[-1]) != idx.numel() or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"{what} offsets must be non-decreasing from 0 to len({what} ids)")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_cols):
+        raise ValueError(f"{what} id out of [0, {n_cols})")
+
+
+def _usercf_inputs(i_off, i_users, u_off, u_items, act, pen):
+    dev = _dev(i_off, i_users, u_off, u_items, act, pen)
+    _need(i_off, torch.int64, name="i_off")
+    _need(u_off, torch.int64, name="u_off")
+    n = i_users.numel()
+    _need(i_users, torch.int32, (n,), "i_users")
+    _need(u_items, torch.int32, (n,), "u_items")
+    n_items, n_users = i_off.numel() - 1, u_off.numel() - 1
+    _need(act, torch.float64, (n_users,), "act")
+    _need(pen, torch.float64, (n_items,), "pen")
+    _csr_ok(i_off, i_users, n_users, "i_users")
+    _csr_ok(u_off, u_items, n_items, "u_items")
+    _finite(act, "act")
+    _finite(pen, "pen")
+    if n and n_users >= 2**31 - 1:
+        raise ValueError("n_users must be < 2^31 - 1")
+    # every user's clicks sorted by item: the duplicate-click test bisects them
+    if n > 1:
+        row = torch.repeat_interleave(torch.arange(n_users, device=dev), u_off[1:] - u_off[:-1])
+        if bool(((row[1:] == row[:-1]) & (u_items[1:] < u_items[:-1])).any()):
+            raise ValueError("u_items must be sorted by item inside every user")
+    return dev, n_items, n_users, n
+
+
+def usercf_topn(i_off, i_users, u_off, u_items, act, pen, topn=20, workspace=None):
+    """UserCF similarity (user_cf.py:31-66), each user's top-n neighbours by
+    (value desc, first slot asc) without materialising the u2u matrix.  Dense
+    ids: i_off [I+1] / i_users [N] the item -> user CSR (items ascending,
+    entries in the reference's list order), u_off [U+1] / u_items [N] every
+    user's clicks sorted by item, act [U], pen [I] = 1 / log(n_i + 1) f64.
+    Returns (cols [U, topn] int32 -1 padded, vals [U, topn] f64, cnt [U]
+    int64 click rows, nnz [U] int32 distinct neighbours)."""
+    if not (1 <= topn <= UC_TOPN_MAX):
+        raise NotImplementedError(f"topn must be in [1, {UC_TOPN_MAX}]")
+    dev, n_items, n_users, n = _usercf_inputs(i_off, i_users, u_off, u_items, act, pen)
+    oc = torch.empty((n_users, topn), dtype=torch.int32, device=dev)
+    ov = torch.empty((n_users, topn), dtype=torch.float64, device=dev)
+    cnt = torch.empty(n_users, dtype=torch.int64, device=dev)
+    nnz = torch.empty(n_users, dtype=torch.int32, device=dev)
+    nb = _lib.lib().nrk_usercf_workspace_bytes(n_users, n, int(topn))
+    ws = workspace if workspace is not None else torch.empty(nb, dtype=torch.uint8, device=dev)
+    _lib.call("nrk_usercf_topn", _ptr(i_off), n_items, _ptr(i_users), _ptr(u_off), n_users, _ptr(u_items), n,
+              _ptr(act), _ptr(pen), int(topn), _ptr(oc), _ptr(ov), _ptr(cnt), _ptr(nnz), _ptr(ws), ws.numel(),
+              _stream())
+    return oc, ov, cnt, nnz
+
+
+def usercf_sim(i_off, i_users, u_off, u_items, act, pen, nnz):
+    """Every entry of every u2u row (small logs, tests): nnz from usercf_topn.
+    Returns (row_off [U+1] int64, v int32, value f64, first int64), a row's
+    entries in no particular order (sort by first for the dict order)."""
+    dev, n_items, n_users, n = _usercf_inputs(i_off, i_users, u_off, u_items, act, pen)
+    _need(nnz, torch.int32, (n_users,), "nnz")
+    row_off = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+    row_off[1:] = torch.cumsum(nnz.to(torch.int64), 0)
+    total = int(row_off[-1])
+    if total >= 2**31:
+        raise ValueError("the u2u matrix has >= 2^31 entries")
+    cap = max(total, 1)
+    ov = torch.empty(cap, dtype=torch.int32, device=dev)
+    os_ = torch.empty(cap, dtype=torch.float64, device=dev)
+    of = torch.empty(cap, dtype=torch.int64, device=dev)
+    nb = _lib.lib().nrk_usercf_workspace_bytes(n_users, n, 1)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    _lib.call("nrk_usercf_sim", _ptr(i_off), n_items, _ptr(i_users), _ptr(u_off), n_users, _ptr(u_items), n,
+              _ptr(act), _ptr(pen), _ptr(row_off), total, _ptr(ov), _ptr(os_), _ptr(of), _ptr(ws), ws.numel(),
+              _stream())
+    return row_off, ov[:total], os_[:total], of[:total]
+
+
+def usercf_recall(q_slot, offsets, items, nbr_cols, nbr_vals, nbr_cnt, loc_w, created, hot, topk,
+                  created_alpha=0.8, emb_cols=None, emb_vals=None, emb_cnt=None):
+    """UserCFRecaller.recall (usercf_recaller.py:37-118) for every query user at
+    once.  Dense ids: q_slot [Q] int64 (CSR row or -1 = cold start),
+    offsets / items = the user_item_time_dict CSR, nbr_* = per-user top-n
+    neighbour rows [U, topn], loc_w [U] f64, created [I] f64, hot [H] int32,
+    optional emb_* [I, ke].  Returns itemcf_recall's four outputs."""
+    _dev(q_slot, offsets, items, nbr_cols, nbr_vals, nbr_cnt, loc_w, created, hot, emb_cols, emb_vals, emb_cnt)
+    _need(q_slot, torch.int64, name="q_slot")
+    _need(offsets, torch.int64, name="offsets")
+    _need(items, torch.int32, name="items")
+    _need(nbr_cols, torch.int32, name="nbr_cols")
+    if nbr_cols.dim() != 2 or nbr_cols.shape[1] < 1:
+        raise ValueError("nbr_cols must be [n_users, topn]")
+    n_users, topn = nbr_cols.shape
+    if offsets.numel() != n_users + 1:
+        raise ValueError("offsets must have n_users + 1 entries")
+    _need(nbr_vals, torch.float64, (n_users, topn), "nbr_vals")
+    _need(nbr_cnt, torch.int32, (n_users,), "nbr_cnt")
+    _need(loc_w, torch.float64, (n_users,), "loc_w")
+    _need(created, torch.float64, name="created")
+    _need(hot, torch.int32, name="hot")
+    n_items = created.numel()
+    if n_items < 1:
+        raise ValueError("created must have one entry per item")
+    _csr_ok(offsets, items, n_items, "items")
+    if hot.numel() and (int(hot.min()) < 0 or int(hot.max()) >= n_items):
+        raise ValueError("hot item out of range")
+    if q_slot.numel() and (int(q_slot.min()) < -1 or int(q_slot.max()) >= n_users):
+        raise ValueError("q_slot out of [-1, n_users)")
+    if n_users:
+        if int(nbr_cnt.min()) < 0 or int(nbr_cnt.max()) > topn:
+            raise ValueError("nbr_cnt out of [0, topn]")
+        valid = torch.arange(topn, device=nbr_cols.device)[None, :] < nbr_cnt[:, None]
+        if bool((valid & ((nbr_cols < 0) | (nbr_cols >= n_users))).any()):
+            raise ValueError("neighbour row out of [0, n_users)")
+    ke = 0
+    if emb_cols is not None:
+        ke = emb_cols.shape[1]
+        _need(emb_cols, torch.int32, (n_items, ke), "emb_cols")
+        _need(emb_vals, torch.float64, (n_items, ke), "emb_vals")
+        _need(emb_cnt, torch.int32, (n_items,), "emb_cnt")
+        if n_items and (int(emb_cnt.min()) < 0 or int(emb_cnt.max()) > ke):
+            raise ValueError("emb_cnt out of [0, ke]")
+    if not (1 <= topk <= CF_TOPK_MAX):
+        raise NotImplementedError(f"topk must be in [1, {CF_TOPK_MAX}]")
+    nq = q_slot.numel()
+    dev = q_slot.device
+    cand_off = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    _lib.call("nrk_usercf_recall_offsets", _ptr(q_slot), nq, _ptr(offsets), _ptr(nbr_cols), _ptr(nbr_cnt), topn,
+              _ptr(cand_off), _stream())
+    n_cand = int(cand_off[nq].item())
+    ws = torch.empty(_lib.lib().nrk_usercf_recall_workspace_bytes(n_cand), dtype=torch.uint8, device=dev)
+    oi = torch.empty((nq, topk), dtype=torch.int32, device=dev)
+    osc = torch.empty((nq, topk), dtype=torch.float64, device=dev)
+    osrc = torch.empty((nq, topk), dtype=torch.int32, device=dev)
+    ocnt = torch.empty(nq, dtype=torch.int32, device=dev)
+    _lib.call("nrk_usercf_recall", _ptr(q_slot), nq, _ptr(offsets), _ptr(items), _ptr(nbr_cols), _ptr(nbr_vals),
+              _ptr(nbr_cnt), topn, _ptr(loc_w), _ptr(created), n_items, _ptr(hot), hot.numel(), _ptr(emb_cols),
+              _ptr(emb_vals), _ptr(emb_cnt), ke, float(created_alpha), _ptr(cand_off), n_cand, int(topk), _ptr(oi),
+              _ptr(osc), _ptr(osrc), _ptr(ocnt), _ptr(ws), ws.numel(), _stream())
+    return oi, osc, osrc, ocnt
+
+
 def din_assemble(rec_rows, rec_scores, user_feat, item_feat, user_hist, hist_len, u0, nu, k_use=30, skip=1,
                  n_ctx=16, ctx_bins=10, score_lo=-1.0, score_hi=1.0, seed=23, out=None, validate=True,
                  ctx_width=None):
