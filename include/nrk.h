@@ -78,6 +78,72 @@ int nrk_tt_item_fwd(const float* item_table, int64_t n_item_rows, int dim, const
                     int64_t n, float* out, nrk_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* YouTubeDNN training (youtubednn_recaller.py:211-423)                   */
+/* ---------------------------------------------------------------------- */
+
+/* Shapes as nrk_tt_user_fwd_layers (dim in {16, 32, 64}, 1 to 8 layers of
+ * width <= 256, the last equal to dim, seq_len in [1, 64]); batch in
+ * [1, 8192].  Weights packed per layer W_l [widths[l], in_l] then b_l.
+ *
+ * A sample is (user, pos, target, label) over the click log in CSR form
+ * (log_off int64 [n_user_rows + 1], log_items int32, each row in time order):
+ * its history is log_items[log_off[user] : log_off[user] + min(pos, seq_len)]
+ * (collate_fn :43-83), pos >= 1. */
+size_t nrk_tt_train_workspace_bytes(int64_t n_user_rows, int64_t n_item_rows, int dim, int n_layers,
+                                    const int* widths, int seq_len, int batch);
+
+/* One batch: forward (train mode), mean BCE-with-logits loss and backward.
+ *   loss     device float: the mean over the batch
+ *   w_grad   dense gradient of the packed weights
+ *   u_rows / u_vals / u_count   gradient of the user table as a compact list:
+ *            *u_count ascending unique rows, u_vals [*u_count, dim]
+ *            (capacity batch rows)
+ *   i_rows / i_vals / i_count   the same for the item table (capacity
+ *            batch * (seq_len + 1) rows)
+ * Dropout (p in [0, 1), every layer, scale 1 / (1 - p)) keeps unit o of
+ * layer l for sample b of the batch iff the counter-based generator of
+ * nrk_tt_dropout_mask says so for (seed, step, l, b, o); p == 0 draws nothing.
+ * Every output is bitwise reproducible: no floating-point atomics, the
+ * batch sums and the per-row sums run in a fixed order. */
+int nrk_tt_train_grad(const float* user_table, int64_t n_user_rows, const float* item_table,
+                      int64_t n_item_rows, int dim, const float* weights, int n_layers, const int* widths,
+                      const int64_t* log_off, const int32_t* log_items, const int32_t* s_user,
+                      const int32_t* s_pos, const int32_t* s_target, const float* s_label, int batch,
+                      int seq_len, float p, uint64_t seed, int64_t step, float* loss, float* w_grad,
+                      int32_t* u_rows, float* u_vals, int32_t* u_count, int32_t* i_rows, float* i_vals,
+                      int32_t* i_count, void* workspace, size_t workspace_bytes, nrk_stream_t stream);
+
+/* out [batch, width] fp32: 1 where the generator keeps the unit, else 0. */
+int nrk_tt_dropout_mask(uint64_t seed, int64_t step, int layer, int batch, int width, float p, float* out,
+                        nrk_stream_t stream);
+
+/* One torch.optim.Adam step (no weight decay, no amsgrad) with dense
+ * semantics over the packed weights and both tables, in
+ * _single_tensor_adam's operation order; t is the 1-based step number.
+ * Rows absent from the compact lists have g = 0 and are still updated; a
+ * row whose m, v and g are all zero is left untouched.  Moments are fp32
+ * buffers of the parameters' shapes, owned by the caller. */
+int nrk_tt_adam_step(float* weights, float* w_m, float* w_v, const float* w_grad, int64_t n_weights,
+                     float* user_table, float* u_m, float* u_v, int64_t n_user_rows, const int32_t* u_rows,
+                     const float* u_vals, const int32_t* u_count, float* item_table, float* i_m, float* i_v,
+                     int64_t n_item_rows, const int32_t* i_rows, const float* i_vals, const int32_t* i_count,
+                     int dim, double lr, double beta1, double beta2, double eps, int64_t t,
+                     nrk_stream_t stream);
+
+/* _prepare_data (:230-300) on the device.  The count query writes pos_off
+ * int64 [n_users + 1]: the exclusive prefix of each user's number of training
+ * positives (n clicks, n >= 2: positions 1 .. n - max(1, int(0.2 n)) - 1), so
+ * pos_off[n_users] is the number of positives.  nrk_tt_make_samples then
+ * writes n_pos * (1 + negsample) samples in (user, pos) order: each positive
+ * (label 1) followed by its negsample negatives (label 0, same user and pos,
+ * target uniform over pool[0 .. n_pool) with replacement). */
+int nrk_tt_make_samples_count(const int64_t* log_off, int64_t n_users, int64_t* pos_off, nrk_stream_t stream);
+int nrk_tt_make_samples(const int64_t* log_off, const int32_t* log_items, int64_t n_users,
+                        const int64_t* pos_off, int64_t n_pos, int negsample, const int32_t* pool,
+                        int64_t n_pool, uint64_t seed, int32_t* s_user, int32_t* s_pos, int32_t* s_target,
+                        float* s_label, nrk_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Brute-force inner-product top-K (replaces faiss.IndexFlatIP)           */
 /* ---------------------------------------------------------------------- */
 

@@ -29,6 +29,14 @@ SIGNATURES = {
     "nrk_tt_user_fwd": (INT, [P, I64, P, I64, INT, P, P, P, I64, INT, P, P, INT, P, P, INT, P, P]),
     "nrk_tt_user_fwd_layers": (INT, [P, I64, P, I64, INT, P, P, P, I64, INT, P, INT, P, P, P]),
     "nrk_tt_item_fwd": (INT, [P, I64, INT, P, I64, P, P]),
+    "nrk_tt_train_workspace_bytes": (SZ, [I64, I64, INT, INT, P, INT, INT]),
+    "nrk_tt_train_grad": (INT, [P, I64, P, I64, INT, P, INT, P, P, P, P, P, P, P, INT, INT, ctypes.c_float,
+                                ctypes.c_uint64, I64, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "nrk_tt_dropout_mask": (INT, [ctypes.c_uint64, I64, INT, INT, INT, ctypes.c_float, P, P]),
+    "nrk_tt_adam_step": (INT, [P, P, P, P, I64, P, P, P, I64, P, P, P, P, P, P, I64, P, P, P, INT,
+                               F64, F64, F64, F64, I64, P]),
+    "nrk_tt_make_samples_count": (INT, [P, I64, P, P]),
+    "nrk_tt_make_samples": (INT, [P, P, I64, P, I64, INT, P, I64, ctypes.c_uint64, P, P, P, P, P]),
     "nrk_ip_catalog_bytes": (SZ, [I64, INT]),
     "nrk_ip_catalog_build": (INT, [P, I64, INT, P, P]),
     "nrk_ip_topk_workspace_bytes": (SZ, [I64, I64, INT, INT]),

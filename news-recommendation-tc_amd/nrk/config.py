@@ -25,6 +25,10 @@ class RecallConfig:
     youtubednn_seq_max_len: int = 30
     youtubednn_embedding_dim: int = 16
     youtubednn_hidden_units: List[int] = field(default_factory=lambda: [64, 16])
+    youtubednn_negsample: int = 4  # negatives per positive (config.py:39)
+    youtubednn_epochs: int = 1
+    youtubednn_batch_size: int = 256
+    youtubednn_learning_rate: float = 0.001
     youtubednn_topk: int = 20
     fuse_topk: int = 30
     loc_alpha: float = 1.0

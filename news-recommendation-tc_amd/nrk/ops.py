@@ -131,8 +131,195 @@ def tt_item_fwd(item_table, ids):
     return out
 
 
+# --------------------------------------------------------- tower training --
+TT_MAX_BATCH = 8192
+_tt_ws_cache = {}
+
+
+def _tt_ws(dev, nbytes):
+    """One workspace per device, grown to the largest request (a training loop
+    asks for the same size every step)."""
+    ws = _tt_ws_cache.get(dev)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _tt_ws_cache[dev] = ws
+    return ws
+
+
+def tt_pack_layers(layers):
+    """[(W_l, b_l), ...] -> (packed fp32 vector, widths): the weight layout of
+    nrk_tt_user_fwd_layers and the training entry points."""
+    return (torch.cat([t.reshape(-1) for wb in layers for t in wb]).contiguous(),
+            [int(w.shape[0]) for w, _ in layers])
+
+
+def tt_unpack_layers(weights, widths, dim):
+    out, off, fan_in = [], 0, 2 * dim
+    for w in widths:
+        out.append((weights[off:off + w * fan_in].view(w, fan_in), weights[off + w * fan_in:off + w * fan_in + w]))
+        off += w * fan_in + w
+        fan_in = w
+    return out
+
+
+def _tt_n_weights(widths, dim):
+    n, fan_in = 0, 2 * dim
+    for w in widths:
+        n += w * (fan_in + 1)
+        fan_in = w
+    return n
+
+
+class TtGrads:
+    """Outputs of tt_train_grad.  ``loss`` [1]; ``w_grad`` dense over the
+    packed weights; each table's gradient as ``*_count`` [1] ascending unique
+    ``*_rows`` with ``*_vals`` [rows, dim] (the buffers have the capacity of
+    the batch; ``user_grad()`` / ``item_grad()`` slice them, one sync)."""
+
+    def __init__(self, dev, batch, seq_len, dim, n_weights):
+        f = dict(dtype=torch.float32, device=dev)
+        i = dict(dtype=torch.int32, device=dev)
+        self.batch, self.seq_len, self.dim = batch, seq_len, dim
+        self.loss = torch.zeros(1, **f)
+        self.w_grad = torch.empty(n_weights, **f)
+        self.u_rows, self.u_vals, self.u_count = torch.empty(batch, **i), torch.empty((batch, dim), **f), torch.zeros(1, **i)
+        cap = batch * (seq_len + 1)
+        self.i_rows, self.i_vals, self.i_count = torch.empty(cap, **i), torch.empty((cap, dim), **f), torch.zeros(1, **i)
+
+    def user_grad(self):
+        n = int(self.u_count)
+        return self.u_rows[:n], self.u_vals[:n]
+
+    def item_grad(self):
+        n = int(self.i_count)
+        return self.i_rows[:n], self.i_vals[:n]
+
+
+def tt_check_samples(n_user_rows, n_item_rows, log_off, log_items, s_user, s_pos, s_target, seq_len):
+    """Range checks of a click log and samples over it (device syncs): what
+    tt_train_grad's kernels trust."""
+    if int(log_off[0]) != 0 or int(log_off[-1]) != log_items.shape[0] or bool((log_off[1:] < log_off[:-1]).any()):
+        raise ValueError("log_off is not a CSR offset vector over log_items")
+    if log_items.numel() and (int(log_items.min()) < 0 or int(log_items.max()) >= n_item_rows):
+        raise ValueError("log_items out of [0, n_item_rows)")
+    if not s_user.numel():
+        return
+    if int(s_user.min()) < 0 or int(s_user.max()) >= n_user_rows:
+        raise ValueError("s_user out of [0, n_user_rows)")
+    if int(s_target.min()) < 0 or int(s_target.max()) >= n_item_rows:
+        raise ValueError("s_target out of [0, n_item_rows)")
+    su = s_user.long()
+    rowlen = log_off[su + 1] - log_off[su]
+    if int(s_pos.min()) < 1 or bool((s_pos.long().clamp(max=seq_len) > rowlen).any()):
+        raise ValueError("s_pos must be >= 1 and min(s_pos, seq_len) within the user's log row")
+
+
+def tt_train_grad(user_table, item_table, weights, widths, log_off, log_items, s_user, s_pos, s_target, s_label,
+                  seq_len, p: float = 0.0, seed: int = 0, step: int = 0, validate: bool = True, out=None, loss=None):
+    """One YoutubeDNN training batch (youtubednn_recaller.py:390-411 without the
+    optimiser): forward in train mode, mean BCE-with-logits loss, backward.
+    ``weights`` / ``widths`` as tt_pack_layers; the click log as CSR
+    (``log_off`` int64 [U + 1], ``log_items`` int32, rows in time order); a
+    sample b is (s_user, s_pos, s_target, s_label)[b] and its history the first
+    min(s_pos, seq_len) items of its user's row.  ``validate`` range-checks the
+    indices (device syncs); a loop over samples it validated once passes False.
+    ``out``: a TtGrads of the same shapes to reuse; ``loss``: a fp32 [1] device
+    tensor (e.g. a slice of a per-step loss vector) to write instead of out.loss."""
+    import ctypes
+
+    dev = _dev(user_table, item_table, weights, log_off, log_items, s_user, s_pos, s_target, s_label, loss)
+    U, D = user_table.shape
+    I = item_table.shape[0]
+    B = s_user.shape[0]
+    _need(user_table, torch.float32, name="user_table")
+    _need(item_table, torch.float32, (I, D), "item_table")
+    _need(weights, torch.float32, (_tt_n_weights(widths, D),), "weights")
+    _need(log_off, torch.int64, (U + 1,), "log_off")
+    _need(log_items, torch.int32, name="log_items")
+    _need(s_user, torch.int32, (B,), "s_user")
+    _need(s_pos, torch.int32, (B,), "s_pos")
+    _need(s_target, torch.int32, (B,), "s_target")
+    _need(s_label, torch.float32, (B,), "s_label")
+    if loss is not None:
+        _need(loss, torch.float32, (1,), "loss")
+    if validate and B:
+        tt_check_samples(U, I, log_off, log_items, s_user, s_pos, s_target, seq_len)
+    wv = (ctypes.c_int * len(widths))(*widths)
+    wp = ctypes.cast(wv, _P)
+    nbytes = _lib.lib().nrk_tt_train_workspace_bytes(U, I, D, len(widths), wp, seq_len, B)
+    if not nbytes:  # shapes outside the compiled variants: the query left the reason in nrk_last_error
+        raise ValueError("nrk_tt_train_workspace_bytes: " + _lib.lib().nrk_last_error().decode(errors="replace"))
+    ws = _tt_ws(dev, nbytes)
+    if out is None:
+        out = TtGrads(dev, B, seq_len, D, weights.numel())
+    elif (out.batch, out.seq_len, out.dim, out.w_grad.numel()) != (B, seq_len, D, weights.numel()):
+        raise ValueError("out: a TtGrads of another shape")
+    _lib.call("nrk_tt_train_grad", _ptr(user_table), U, _ptr(item_table), I, D, _ptr(weights), len(widths), wp,
+              _ptr(log_off), _ptr(log_items), _ptr(s_user), _ptr(s_pos), _ptr(s_target), _ptr(s_label), B,
+              seq_len, float(p), int(seed) & (2 ** 64 - 1), int(step), _ptr(out.loss if loss is None else loss),
+              _ptr(out.w_grad), _ptr(out.u_rows), _ptr(out.u_vals), _ptr(out.u_count), _ptr(out.i_rows),
+              _ptr(out.i_vals), _ptr(out.i_count), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def tt_dropout_mask(seed: int, step: int, layer: int, batch: int, width: int, p: float, device="cuda"):
+    """The 0 / 1 keep mask [batch, width] tt_train_grad applies to ``layer``'s
+    outputs at (seed, step): a pure function of its counters."""
+    out = torch.empty((batch, width), dtype=torch.float32, device=device)
+    _lib.call("nrk_tt_dropout_mask", int(seed) & (2 ** 64 - 1), int(step), layer, batch, width, float(p), _ptr(out),
+              _stream())
+    return out
+
+
+def tt_adam_step(weights, w_m, w_v, user_table, u_m, u_v, item_table, i_m, i_v, grads: TtGrads, t: int,
+                 lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+    """One torch.optim.Adam step (dense semantics) in place over the packed
+    weights and both tables from tt_train_grad's outputs; ``t`` is the 1-based
+    step number, the moments are fp32 tensors of the parameters' shapes."""
+    _dev(weights, w_m, w_v, user_table, u_m, u_v, item_table, i_m, i_v, grads.w_grad, grads.u_rows, grads.u_vals,
+         grads.i_rows, grads.i_vals)
+    D = user_table.shape[1]
+    for name, ts in (("weights", (weights, w_m, w_v, grads.w_grad)), ("user_table", (user_table, u_m, u_v)),
+                     ("item_table", (item_table, i_m, i_v))):
+        for x in ts:
+            _need(x, torch.float32, ts[0].shape, name)
+    if item_table.shape[1] != D or grads.dim != D:
+        raise ValueError("tables and gradients of different dims")
+    _lib.call("nrk_tt_adam_step", _ptr(weights), _ptr(w_m), _ptr(w_v), _ptr(grads.w_grad), weights.numel(),
+              _ptr(user_table), _ptr(u_m), _ptr(u_v), user_table.shape[0], _ptr(grads.u_rows), _ptr(grads.u_vals),
+              _ptr(grads.u_count), _ptr(item_table), _ptr(i_m), _ptr(i_v), item_table.shape[0], _ptr(grads.i_rows),
+              _ptr(grads.i_vals), _ptr(grads.i_count), D, float(lr), float(betas[0]), float(betas[1]), float(eps),
+              int(t), _stream())
+
+
+def tt_make_samples(log_off, log_items, negsample: int = 0, pool=None, seed: int = 0):
+    """_prepare_data's training set (youtubednn_recaller.py:230-297) before
+    the shuffle: per user with n >= 2 clicks and position i in
+    [1, n - max(1, int(0.2 n))), the positive (user, i, row[i], 1) followed by
+    ``negsample`` negatives (user, i, uniform draw from ``pool``, 0).
+    Returns (s_user, s_pos, s_target int32, s_label fp32)."""
+    dev = _dev(log_off, log_items, pool)
+    U = log_off.shape[0] - 1
+    _need(log_off, torch.int64, name="log_off")
+    _need(log_items, torch.int32, name="log_items")
+    if negsample:
+        if pool is None or not pool.numel():
+            raise ValueError("negatives need a non-empty pool")
+        _need(pool, torch.int32, name="pool")
+    pos_off = torch.empty(U + 1, dtype=torch.int64, device=dev)
+    _lib.call("nrk_tt_make_samples_count", _ptr(log_off), U, _ptr(pos_off), _stream())
+    n_pos = int(pos_off[-1])
+    n = n_pos * (1 + negsample)
+    s_user, s_pos, s_target = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    s_label = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.call("nrk_tt_make_samples", _ptr(log_off), _ptr(log_items), U, _ptr(pos_off), n_pos, negsample, _ptr(pool),
+              pool.numel() if pool is not None else 0, int(seed) & (2 ** 64 - 1), _ptr(s_user), _ptr(s_pos),
+              _ptr(s_target), _ptr(s_label), _stream())
+    return s_user, s_pos, s_target, s_label
+
+
 # ------------------------------------------------------------------ top-k --
-IP_KFAST = 128   # k on the MFMA screen path (csrc/ip_topk.hip); larger k takes the exact path
+IP_KFAST = 128  # k on the MFMA screen path (csrc/ip_topk.hip); larger k takes the exact path
 IP_KMAX = 2048   # largest k compiled
 CF_TOPK_MAX = 2048  # nrk_itemcf_topn / nrk_itemcf_recall (register path <= 64, LDS path above)
 

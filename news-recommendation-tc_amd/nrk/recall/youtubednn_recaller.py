@@ -11,8 +11,12 @@ What changes is underneath: the user/item towers run as HIP kernels
 (nrk_tt_user_fwd / nrk_tt_item_fwd), the Faiss IndexFlatIP becomes a device
 catalog (nrk_ip_catalog_build) and ``batch_recall`` is ONE device top-k call
 for the whole user list (nrk_ip_topk) instead of one Faiss search per user.
-Training (:211-423) is outside the hot path: load trained weights with
-``load_model`` or precomputed embeddings with ``from_embeddings``.
+``train`` (:211-423) runs on the GPU as well: the samples are generated on the
+device (nrk_tt_make_samples), every step is one fused forward + loss +
+backward (nrk_tt_train_grad) and one dense-semantics Adam sweep
+(nrk_tt_adam_step), with no host synchronisation between steps; it ends
+through ``load_model``.  Weights trained elsewhere still load with
+``load_model``, precomputed embeddings with ``from_embeddings``.
 """
 from __future__ import annotations
 
@@ -50,6 +54,10 @@ class YoutubeDNNRecaller(BaseRecaller):
         self.item_embeddings = None  # torch [I, D] on device
         self.catalog = None          # ops.Catalog = the Faiss index
         self._item_raw = None        # np [I] row -> raw id (quirk mapping)
+        self.negsample = int(getattr(self.config, "youtubednn_negsample", 4))
+        self.dropout = 0.2           # nn.Dropout(0.2) after every layer (:110)
+        self._trained = None         # (user table, item table, packed weights, widths) after training
+        self.epoch_losses: List[float] = []
 
     # -------------------------------------------------------------- setup --
     @classmethod
@@ -93,6 +101,124 @@ class YoutubeDNNRecaller(BaseRecaller):
                              f(profile.astype(np.int32)))
         self._set_state(ue, ie, user_raw, item_raw)
         return self
+
+    # ----------------------------------------------------------- training --
+    def train(self, click_df, epochs: int = 1, batch_size: int = 256, learning_rate: float = 0.001, seed=None):
+        """YoutubeDNNRecaller.train (:312-423) on the GPU.  Label encoding as
+        load_model's (:324-353); _prepare_data's samples (:230-300) made on the
+        device from the time-ordered click log, negatives uniform over the
+        log's items, shuffled by a device permutation before every epoch (the
+        DataLoader's shuffle=True); _init_weights' initialisation (:119-127);
+        BCEWithLogitsLoss + Adam(lr) (:381-412).  ``seed`` (default
+        config.random_seed) fixes the initialisation, the negatives, the
+        shuffles and the dropout masks: two runs with one seed are
+        bit-identical.  Prints the average loss per epoch and finishes through
+        load_model, so recall / batch_recall work afterwards."""
+        seed = int(getattr(self.config, "random_seed", 23) if seed is None else seed)
+        user_col = np.asarray(click_df["user_id"], np.int64)
+        item_col = np.asarray(click_df["click_article_id"], np.int64)
+        ts = np.asarray(click_df["click_timestamp"], np.int64)
+        u_classes, u_enc = np.unique(user_col, return_inverse=True)
+        i_classes, i_enc = np.unique(item_col, return_inverse=True)
+        # sort_values("click_timestamp") then groupby user (:230, :248); equal stamps keep their row order
+        order = np.lexsort((np.arange(len(ts)), ts, u_enc))
+        log_off = np.concatenate([[0], np.cumsum(np.bincount(u_enc, minlength=len(u_classes)))]).astype(np.int64)
+        dev = self.device
+        log_off_d = torch.as_tensor(log_off).to(dev)
+        log_items_d = torch.as_tensor(i_enc[order].astype(np.int32)).to(dev)
+        pool = torch.arange(len(i_classes), dtype=torch.int32, device=dev)  # click_article_id.unique() (:233)
+        state = self.init_state(len(u_classes), len(i_classes), seed)
+        samples = ops.tt_make_samples(log_off_d, log_items_d, self.negsample, pool, seed)
+        if not samples[0].numel():
+            raise ValueError("no training samples: every user has fewer than 3 clicks")
+        print("Training YoutubeDNN model...")
+        self.train_on_samples(state, log_off_d, log_items_d, *samples, batch_size=batch_size, epochs=epochs,
+                              learning_rate=learning_rate, dropout=self.dropout, seed=seed, shuffle=True, verbose=True)
+        self.load_model(self.state_dict(), click_df)
+        print("Training completed!")
+        return self
+
+    def init_state(self, n_users: int, n_items: int, seed: int = 0):
+        """YoutubeDNN._init_weights (:119-127): xavier-uniform Linear weights,
+        zero biases, N(0, 0.01) embeddings, under the reference's key names."""
+        g = torch.Generator().manual_seed(int(seed))
+        D = self.embedding_dim
+        sd = {"user_embedding.weight": torch.empty(n_users, D).normal_(0.0, 0.01, generator=g),
+              "item_embedding.weight": torch.empty(n_items, D).normal_(0.0, 0.01, generator=g)}
+        fan_in = 2 * D
+        for l, w in enumerate(self.hidden_units):
+            a = (6.0 / (fan_in + w)) ** 0.5
+            sd[f"user_tower.{3 * l}.weight"] = torch.empty(w, fan_in).uniform_(-a, a, generator=g)
+            sd[f"user_tower.{3 * l}.bias"] = torch.zeros(w)
+            fan_in = w
+        return sd
+
+    def train_on_samples(self, state_dict, log_off, log_items, s_user, s_pos, s_target, s_label,
+                         batch_size: int = 256, epochs: int = 1, learning_rate: float = 0.001,
+                         dropout: float = 0.2, seed: int = 0, shuffle: bool = False, verbose: bool = False):
+        """The training loop over explicit samples from an initial state_dict
+        (the reference module's keys): consecutive batches of ``batch_size``
+        (the last one short, drop_last=False), every epoch in the given order
+        unless ``shuffle``.  Returns the per-step losses (fp32, on the host,
+        read from the device once per epoch); the trained parameters are then
+        in ``state_dict()``."""
+        dev = self.device
+        t32 = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt).contiguous()  # noqa: E731
+        log_off, log_items = t32(log_off, torch.int64), t32(log_items, torch.int32)
+        s_user, s_pos, s_target = (t32(a, torch.int32) for a in (s_user, s_pos, s_target))
+        s_label = t32(s_label, torch.float32)
+        sd = {k: t32(v.detach() if torch.is_tensor(v) else v, torch.float32) for k, v in state_dict.items()}
+        n_layers = len([k for k in sd if k.startswith("user_tower.") and k.endswith(".weight")])
+        ue, ie = sd["user_embedding.weight"].clone(), sd["item_embedding.weight"].clone()
+        weights, widths = ops.tt_pack_layers([(sd[f"user_tower.{3 * l}.weight"], sd[f"user_tower.{3 * l}.bias"])
+                                              for l in range(n_layers)])
+        moments = [torch.zeros_like(x) for x in (weights, weights, ue, ue, ie, ie)]
+        n, T, D = s_user.numel(), self.seq_max_len, ue.shape[1]
+        if not 1 <= batch_size <= ops.TT_MAX_BATCH:
+            raise ValueError(f"batch_size must be in [1, {ops.TT_MAX_BATCH}]")
+        if n == 0:
+            raise ValueError("no samples")
+        bounds = [(a, min(n, a + batch_size)) for a in range(0, n, batch_size)]
+        bufs = {b - a: ops.TtGrads(dev, b - a, T, D, weights.numel()) for a, b in (bounds[0], bounds[-1])}
+        # every index is range-checked here, once, so that no step synchronises with the host
+        if log_off.shape[0] != ue.shape[0] + 1:
+            raise ValueError("log_off must have one row per user of the user table")
+        ops.tt_check_samples(ue.shape[0], ie.shape[0], log_off, log_items, s_user, s_pos, s_target, T)
+        gen = torch.Generator(device=dev).manual_seed(int(seed)) if shuffle else None
+        all_losses, step = [], 0
+        self.epoch_losses = []
+        for epoch in range(epochs):
+            cur = (s_user, s_pos, s_target, s_label)
+            if shuffle:
+                perm = torch.randperm(n, device=dev, generator=gen)
+                cur = tuple(a[perm].contiguous() for a in cur)
+            losses = torch.zeros(len(bounds), dtype=torch.float32, device=dev)
+            for s, (a, b) in enumerate(bounds):
+                g = ops.tt_train_grad(ue, ie, weights, widths, log_off, log_items, cur[0][a:b], cur[1][a:b],
+                                      cur[2][a:b], cur[3][a:b], T, p=dropout, seed=seed, step=step,
+                                      validate=False, out=bufs[b - a], loss=losses[s:s + 1])
+                ops.tt_adam_step(weights, moments[0], moments[1], ue, moments[2], moments[3], ie, moments[4],
+                                 moments[5], g, t=step + 1, lr=learning_rate)
+                step += 1
+            host = losses.cpu()  # the epoch's one read of the device
+            all_losses.append(host)
+            self.epoch_losses.append(float(host.double().mean()))
+            if verbose:
+                print(f"Epoch {epoch + 1} - Avg Loss: {self.epoch_losses[-1]:.4f}")
+        self._trained = (ue, ie, weights, widths)
+        return torch.cat(all_losses)
+
+    def state_dict(self):
+        """The trained parameters under the reference module's key names (host
+        tensors): loads into the reference's YoutubeDNN and into load_model."""
+        if self._trained is None:
+            raise ValueError("Model not trained. Call train() first.")
+        ue, ie, weights, widths = self._trained
+        sd = {"user_embedding.weight": ue.cpu(), "item_embedding.weight": ie.cpu()}
+        for l, (w, b) in enumerate(ops.tt_unpack_layers(weights, widths, ue.shape[1])):
+            sd[f"user_tower.{3 * l}.weight"] = w.cpu().clone()
+            sd[f"user_tower.{3 * l}.bias"] = b.cpu().clone()
+        return sd
 
     def _set_state(self, ue, ie, user_raw, item_raw):
         self.user_embeddings = ue
