@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -1623,6 +1624,32 @@ __device__ __forceinline__ uint32_t wave_sort_desc_u32(uint32_t x, int lane) {
     return x;
 }
 
+// the lanes of a wave whose index has bit b (a power of two, up to 64) clear
+constexpr uint64_t lanes_bit_clear(int b) {
+    uint64_t m = 0;
+    for (int l = 0; l < 64; ++l) m |= (uint64_t)((l & b) == 0) << l;
+    return m;
+}
+
+// 64 u64 keys, one per lane, sorted descending: the same network on a register
+// pair.  Per stage two 32-bit lane exchanges, one 64-bit compare and two
+// selects; which lanes keep the larger key is a per-stage constant lane mask
+// xor-ed into the compare mask on the scalar unit.
+__device__ __forceinline__ uint64_t wave_sort_desc_u64(uint64_t x) {
+    static_for<6>([&](auto klc) {
+        constexpr int kl = decltype(klc)::value + 1, k = 1 << kl;
+        static_for<kl>([&](auto jc) {
+            constexpr int j = 1 << (kl - 1 - decltype(jc)::value);
+            // lower = (lane & j) == 0, up = (lane & k) == 0; lower != up: the lane keeps the smaller key
+            constexpr uint64_t KEEP_MIN = lanes_bit_clear(j) ^ lanes_bit_clear(k);
+            const uint64_t y = ((uint64_t)lane_xor<j>((uint32_t)(x >> 32)) << 32) | (uint64_t)lane_xor<j>((uint32_t)x);
+            const bool keep_x = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(x > y) ^ KEEP_MIN);
+            x = keep_x ? x : y;  // equal keys: either
+        });
+    });
+    return x;
+}
+
 // the key of rank r (r < c) of a wave's LDS row of c keys (see lds_ranks):
 // up to 64 keys by one wave sort (~21 exchange stages; the rank count costs
 // ~5 VALU per key per lane), more 64 at a time (a run-time loop: few
@@ -1845,7 +1872,19 @@ constexpr bool REFINE_DIRECT = NRK_REFINE_DIRECT;
 #ifndef NRK_REFINE_WPE
 #define NRK_REFINE_WPE 6
 #endif
-template <int DS4, int SV>
+// dims 16 and 32: the prefilter loads a half-block's contiguous run with one
+// wave load, DS4 / 2 lanes per item (0: a lane per item, four 16-B pieces 64 B
+// apart: 32 cache lines per load instruction instead of 8)
+#ifndef NRK_REFINE_LANES
+#define NRK_REFINE_LANES 1
+#endif
+// callers without out_exact sort up to 64 survivors on one u64 key
+#ifndef NRK_REFINE_KEY64
+#define NRK_REFINE_KEY64 1
+#endif
+// FK: out_e == nullptr, so the final order may be taken on the fp32 score
+// (with the exact sort behind it whenever two fp32 scores tie)
+template <int DS4, int SV, bool FK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ? 2 : DS4 == 0 ? 4 : NRK_REFINE_WPE))) void ip_refine_kernel(
     const float* __restrict__ users, int64_t n_users, const float* __restrict__ items,
     const uint8_t* __restrict__ catalog, int64_t n_items, int dim, int k, int64_t row_offset,
@@ -2002,39 +2041,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         // one exact round: the rows staged through LDS with whole-row
         // coalesced float4 pieces, each lane summing its own row sequentially
         // (the oracle's order).
-        uint4 pc[DSK > 0 ? 2 * DSK : 1];
-        auto band_q = [&](int base) -> uint32_t {
-            int idx = base + lane;
-            idx = idx < nitem ? idx : nitem - 1;
-            return bandq[wave][idx > 0 ? idx >> 4 : 0];
-        };
-        // the prefilter reads the half-block-major copy: item r of band
-        // entry qv is the 8 DS4-B row at ((qv * 16 + r) * 8 DS4), the 16
-        // items of a half-block one contiguous run
+        constexpr bool LANES = NRK_REFINE_LANES && (DS4 == 4 || DS4 == 8);
         const uint8_t* hbc = catalog ? catalog + catalog_hb_offset(n_items, 4 * DS4) : nullptr;
-        int64_t hoff = 0;
-        auto item_row = [&](int base, uint32_t qv, int32_t& row, bool& inb) {
-            const int idx = base + lane, r = idx & 15;
-            const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
-            inb = idx < nitem && rr < n_items;
-            row = inb ? (int32_t)rr : 0;
-            hoff = inb ? ((int64_t)qv * 16 + r) * (8 * DS4) : 0;
-        };
-        auto pieces = [&](int32_t) {
-            if (pre) {
-                const uint8_t* bp = hbc + hoff;
-#pragma unroll
-                for (int st = 0; st < DSK; ++st)
-#pragma unroll
-                    for (int hh = 0; hh < 2; ++hh)
-                        pc[2 * st + hh] = *reinterpret_cast<const uint4*>(bp + 32 * st + 16 * hh);
-            }
-        };
         int kc = 0, ko = 0;  // ring fill / read positions (wave-uniform)
         // rows staged 32 at a time (half the LDS of a whole round: four
         // workgroups per CU instead of three)
         auto exact_round = [&](int m) {
-            const int32_t rl = lane < m ? krow[wave][(ko + lane) & (IP_KRING - 1)] : -1;
+            int32_t rl = lane < m ? krow[wave][(ko + lane) & (IP_KRING - 1)] : -1;
+            if constexpr (LANES) {
+                // the ring holds codes (band position * 16 + r): the catalog
+                // row, and whether it exists, only for the kept items
+                if (rl >= 0) {
+                    const uint32_t qv = bandq[wave][rl >> 4];
+                    const int r = rl & 15;
+                    const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
+                    rl = rr < n_items ? (int32_t)rr : -1;
+                }
+            }
             double sd = 0.0;
             bool keep = false;
             if constexpr (REFINE_DIRECT && DS4 <= 8) {
@@ -2105,45 +2128,163 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
             push(keep, sd, rl);
             ko += m;
         };
-        int32_t row;
-        bool inb;
-        item_row(0, band_q(0), row, inb);
-        pieces(row);
-        uint32_t q1 = band_q(WAVE < nitem ? WAVE : 0);
-        for (int base = 0; base < nitem; base += WAVE) {
-            // (A) fp16 prefilter of this round: every band item's scaled fp16
-            // score from its 64-B packed row, kept when it reaches the cut
-            // (|fp16 score - exact| <= eps as in the screen)
-            bool keep = inb;
-            if (pre && inb) {
-                float acc = 0.0f;
+        if constexpr (LANES) {
+            // (A) one wave load per contiguous KB of the half-block-major copy:
+            // LPI = DS4 / 2 lanes per item (lane l holds 8 dims of item
+            // l / LPI), so a load covers one half-block at dim 32 and two at
+            // dim 16, and touches 8 cache lines.  The band id is wave-uniform
+            // (a readlane of the group's four entries): the address is a
+            // scalar base plus a constant per-lane offset, 32-bit inside the
+            // packed body's 2-GiB bound.  Each lane sums its 8 products with
+            // its 8 user values (registers), the LPI partial sums meet over
+            // lane_xor, and per group of four half-blocks (64 items, LPI
+            // loads) lane l takes load l % LPI's item l / LPI: one compare,
+            // one ballot, one ring push of the code (band position * 16 + r).
+            // The next group's loads are in flight meanwhile.
+            constexpr int LPI = DS4 / 2, HS = 4 / LPI, WL = 16 * LPI;
+            constexpr int LGL = LPI == 4 ? 2 : 1;
+            const int sub = lane & (LPI - 1), itl = lane >> LGL;
+            const uint32_t woff = (uint32_t)(lane & (WL - 1)) * 16u;
+            // ids past the catalog's half-blocks are never loaded (their
+            // items fail the row test of the exact round)
+            const uint32_t nhb1 = (uint32_t)(2 * ((n_items + 31) >> 5)) - 1u;
+            const int ngrp = (nband + 3) >> 2;
+            auto group_q = [&](int g) -> uint32_t {
+                return min(bandq[wave][min(4 * g + (lane & 3), nband - 1)], nhb1);
+            };
+            auto loads = [&](uint32_t qg, uint4(&p)[LPI]) {
 #pragma unroll
-                for (int st = 0; st < DSK; ++st)
-#pragma unroll
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const f16x8 hv = __builtin_bit_cast(f16x8, pc[2 * st + hh]);
-                        const f16x8 uh = *reinterpret_cast<const f16x8*>(&ush[16 * st + 8 * hh]);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            acc = fmaf((float)hv[e], (float)uh[e], acc);  // exact product: fma_mix
+                for (int t = 0; t < LPI; ++t) {
+                    uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)qg, HS * t);
+                    if constexpr (HS == 2) {
+                        const uint32_t q1 = (uint32_t)__builtin_amdgcn_readlane((int)qg, 2 * t + 1);
+                        q = lane < 32 ? q : q1;
                     }
-                keep = acc >= pcut;
+                    p[t] = *reinterpret_cast<const uint4*>(hbc + (q * (uint32_t)(128 * DS4) + woff));
+                }
+            };
+            auto score = [&](const uint4(&p)[LPI]) -> float {
+                // the lane's 8 user values: one LDS read per group (held in
+                // registers across the exact rounds they spilled)
+                const f16x8 uh = *reinterpret_cast<const f16x8*>(&ush[8 * sub]);
+                float a[LPI];
+#pragma unroll
+                for (int t = 0; t < LPI; ++t) {
+                    const f16x8 hv = __builtin_bit_cast(f16x8, p[t]);
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc = fmaf((float)hv[e], (float)uh[e], acc);  // exact product: fma_mix
+                    // lane ^ 1, lane ^ 2 (quad_perm, as lane_xor) in the form
+                    // the compiler folds into the add itself
+                    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, true));
+                    if constexpr (LPI == 4)
+                        acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, true));
+                    a[t] = acc;
+                }
+                float r = (sub & 1) ? a[1] : a[0];
+                if constexpr (LPI == 4) {
+                    const float r2 = (sub & 1) ? a[3] : a[2];
+                    r = (sub & 2) ? r2 : r;
+                }
+                return r;
+            };
+            uint4 pc[LPI] = {};
+            uint32_t qn = 0;  // the next group's band entries
+            if (pre && ngrp > 0) {
+                loads(group_q(0), pc);
+                qn = group_q(ngrp > 1 ? 1 : 0);
             }
-            const int32_t row_cur = row;
-            // next round's rows and packed pieces, then the band entries of
-            // the round after it
-            const int nb = base + WAVE;
-            if (nb < nitem) {
-                item_row(nb, q1, row, inb);
-                pieces(row);
-                q1 = band_q(nb + WAVE < nitem ? nb + WAVE : nb);
+            for (int g = 0; g < ngrp; ++g) {
+                const int hb = 4 * g + HS * sub + (itl >> 4);
+                bool keep = hb < nband;
+                if (pre) {
+                    // every lane sums (the lane_xor adds read the whole quad,
+                    // also where the group's last half-blocks are missing)
+                    const float sc = score(pc);
+                    keep = keep && sc >= pcut;
+                    // the next group's pieces (into the registers just
+                    // summed), then the band entries of the group after it
+                    if (g + 1 < ngrp) {
+                        loads(qn, pc);
+                        qn = group_q(g + 2 < ngrp ? g + 2 : g + 1);
+                    }
+                }
+                const unsigned long long bal = __ballot(keep);
+                if (keep)
+                    krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = hb * 16 + (itl & 15);
+                kc += __popcll(bal);
+                wave_sync_lds();
+                // (B) exact rounds on full 64-row chunks
+                while (kc - ko >= WAVE) exact_round(WAVE);
             }
-            const unsigned long long bal = __ballot(keep);
-            if (keep) krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = row_cur;
-            kc += __popcll(bal);
-            wave_sync_lds();
-            // (B) exact rounds on full 64-row chunks
-            while (kc - ko >= WAVE) exact_round(WAVE);
+        } else {
+            uint4 pc[DSK > 0 ? 2 * DSK : 1];
+            auto band_q = [&](int base) -> uint32_t {
+                int idx = base + lane;
+                idx = idx < nitem ? idx : nitem - 1;
+                return bandq[wave][idx > 0 ? idx >> 4 : 0];
+            };
+            // the prefilter reads the half-block-major copy: item r of band
+            // entry qv is the 8 DS4-B row at ((qv * 16 + r) * 8 DS4), the 16
+            // items of a half-block one contiguous run
+            int64_t hoff = 0;
+            auto item_row = [&](int base, uint32_t qv, int32_t& row, bool& inb) {
+                const int idx = base + lane, r = idx & 15;
+                const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
+                inb = idx < nitem && rr < n_items;
+                row = inb ? (int32_t)rr : 0;
+                hoff = inb ? ((int64_t)qv * 16 + r) * (8 * DS4) : 0;
+            };
+            auto pieces = [&](int32_t) {
+                if (pre) {
+                    const uint8_t* bp = hbc + hoff;
+#pragma unroll
+                    for (int st = 0; st < DSK; ++st)
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh)
+                            pc[2 * st + hh] = *reinterpret_cast<const uint4*>(bp + 32 * st + 16 * hh);
+                }
+            };
+            int32_t row;
+            bool inb;
+            item_row(0, band_q(0), row, inb);
+            pieces(row);
+            uint32_t q1 = band_q(WAVE < nitem ? WAVE : 0);
+            for (int base = 0; base < nitem; base += WAVE) {
+                // (A) fp16 prefilter of this round: every band item's scaled fp16
+                // score from its 64-B packed row, kept when it reaches the cut
+                // (|fp16 score - exact| <= eps as in the screen)
+                bool keep = inb;
+                if (pre && inb) {
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int st = 0; st < DSK; ++st)
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh) {
+                            const f16x8 hv = __builtin_bit_cast(f16x8, pc[2 * st + hh]);
+                            const f16x8 uh = *reinterpret_cast<const f16x8*>(&ush[16 * st + 8 * hh]);
+#pragma unroll
+                            for (int e = 0; e < 8; ++e)
+                                acc = fmaf((float)hv[e], (float)uh[e], acc);  // exact product: fma_mix
+                        }
+                    keep = acc >= pcut;
+                }
+                const int32_t row_cur = row;
+                // next round's rows and packed pieces, then the band entries of
+                // the round after it
+                const int nb = base + WAVE;
+                if (nb < nitem) {
+                    item_row(nb, q1, row, inb);
+                    pieces(row);
+                    q1 = band_q(nb + WAVE < nitem ? nb + WAVE : nb);
+                }
+                const unsigned long long bal = __ballot(keep);
+                if (keep) krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = row_cur;
+                kc += __popcll(bal);
+                wave_sync_lds();
+                // (B) exact rounds on full 64-row chunks
+                while (kc - ko >= WAVE) exact_round(WAVE);
+            }
         }
         while (kc > ko) exact_round(kc - ko < WAVE ? kc - ko : WAVE);
     } else {
@@ -2231,6 +2372,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         // up to 64 survivors (nearly every user at config 2): one per lane, a
         // 64-wide sort -- 21 shuffle stages instead of the SV-wide sort's 28 x
         // SE (finish 1.27 -> 0.93 ms; rank counting over LDS broadcasts: 0.94)
+        if constexpr (FK && NRK_REFINE_KEY64) {
+            // nobody reads the exact score: sort the key (fp32 score's ordered
+            // key, ~row), i.e. (fp32 score desc, row asc).  fp32 rounding is
+            // monotone, so this is the exact order unless two neighbours among
+            // the sorted positions 0..k share an fp32 score; such a user
+            // (ballot below) is sorted again from surv on the exact scores
+            uint64_t key = 0;  // below every real key (fkey is never 0)
+            if (lane < cnt) {
+                const Cand c = surv[wave][lane];
+                key = ((uint64_t)fkey((float)c.s) << 32) | (uint32_t)~c.row;
+            }
+            key = wave_sort_desc_u64(key);
+            const uint32_t hi = (uint32_t)(key >> 32);
+            const uint32_t hi_next = (uint32_t)__shfl_down((int)hi, 1, WAVE);
+            if (!__ballot(lane < k && lane + 1 < cnt && hi == hi_next)) {
+                if (lane < k) {
+                    const bool ok = lane < cnt;  // real keys sort before the padding
+                    out_s[u * k + lane] = ok ? fkey_inv(hi) : -FLT_MAX;
+                    out_r[u * k + lane] = ok ? (int32_t)((int32_t)~(uint32_t)key + row_offset) : -1;
+                }
+                return;
+            }
+        }
         Cand x1[1];
         if (lane < cnt) x1[0] = surv[wave][lane];
         else { x1[0].s = -INFINITY; x1[0].row = INT32_MAX; }
@@ -3055,8 +3219,18 @@ static void launch_exact(const float* users, int64_t n_users, const float* items
                          hipStream_t s) {
     const int ns = next_pow2(std::max(k, 64));
     const size_t lds = (size_t)ns * sizeof(Cand);
-    (void)hipFuncSetAttribute((const void*)ip_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)ip_fallback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // the dynamic-LDS limit of both kernels, raised once per device to the
+    // largest k's sort (it was set again on every finish)
+    static std::atomic<uint64_t> attr_done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t dbit = 1ull << (dev & 63);
+    if (dev >= 64 || !(attr_done.load(std::memory_order_acquire) & dbit)) {
+        const int lds_max = next_pow2(IP_KMAX) * (int)sizeof(Cand);
+        (void)hipFuncSetAttribute((const void*)ip_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        (void)hipFuncSetAttribute((const void*)ip_fallback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        attr_done.fetch_or(dbit, std::memory_order_release);
+    }
     const int grid = (int)std::min<int64_t>(n_users, FB_GRID);
     ip_exact_kernel<<<grid, 256, lds, s>>>(users, items, n_items, dim, k, ns, row_offset, w.ovf_list, w.ovf_count,
                                            out_s, out_r, out_e, w.fbk, w.slow_list, w.ovf_count + 1);
@@ -3222,14 +3396,16 @@ int nrk_ip_topk_finish(const float* users, int64_t n_users, const float* items,
     hipStream_t s = as_stream(stream);
     const int g2 = (int)((n_users + 3) / 4);
     const uint8_t* cat = reinterpret_cast<const uint8_t*>(catalog);
-#define NRK_REFINE(DS4, SV)                                                                                  \
-    ip_refine_kernel<DS4, SV><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset,   \
-                                                 w.cand, w.bandcap, w.cnt, w.ucut, w.ovf_flag, w.ovf_list,   \
-                                                 w.ovf_count, out_scores, out_rows, out_exact)
-#define NRK_REFINE_SV(DS4)                          \
-    do {                                            \
-        if (k <= 64) NRK_REFINE(DS4, 128);          \
-        else NRK_REFINE(DS4, 256);                  \
+#define NRK_REFINE(DS4, SV, FK)                                                                                \
+    ip_refine_kernel<DS4, SV, FK><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset, \
+                                                     w.cand, w.bandcap, w.cnt, w.ucut, w.ovf_flag, w.ovf_list, \
+                                                     w.ovf_count, out_scores, out_rows, out_exact)
+    // the u64 key sort exists where one lane holds one survivor (k <= 64)
+#define NRK_REFINE_SV(DS4)                                  \
+    do {                                                    \
+        if (k > 64) NRK_REFINE(DS4, 256, false);            \
+        else if (out_exact) NRK_REFINE(DS4, 128, false);    \
+        else NRK_REFINE(DS4, 128, true);                    \
     } while (0)
     if (k <= IP_KFAST || n_items == 0) {
         if (dim == 32) NRK_REFINE_SV(8);
@@ -3399,14 +3575,15 @@ int nrk_ip_topk_refine_x(const float* users, int64_t n_users, const float* items
     const uint8_t* cat = reinterpret_cast<const uint8_t*>(catalog);
     const uint2* bd = reinterpret_cast<const uint2*>(band);
     const float2* uc = reinterpret_cast<const float2*>(ucut);
-#define NRK_REFINE(DS4, SV)                                                                                   \
-    ip_refine_kernel<DS4, SV><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset, bd, 0, \
-                                                 nullptr, uc, w.ovf_flag, w.ovf_list, w.ovf_count, out_scores,   \
-                                                 out_rows, out_exact, n_src, src_users, x_cap, src_cnt)
-#define NRK_REFINE_SV(DS4)                 \
-    do {                                   \
-        if (k <= 64) NRK_REFINE(DS4, 128); \
-        else NRK_REFINE(DS4, 256);         \
+#define NRK_REFINE(DS4, SV, FK)                                                                                      \
+    ip_refine_kernel<DS4, SV, FK><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset, bd, 0, \
+                                                     nullptr, uc, w.ovf_flag, w.ovf_list, w.ovf_count, out_scores,   \
+                                                     out_rows, out_exact, n_src, src_users, x_cap, src_cnt)
+#define NRK_REFINE_SV(DS4)                                  \
+    do {                                                    \
+        if (k > 64) NRK_REFINE(DS4, 256, false);            \
+        else if (out_exact) NRK_REFINE(DS4, 128, false);    \
+        else NRK_REFINE(DS4, 128, true);                    \
     } while (0)
     if (dim == 32) NRK_REFINE_SV(8);
     else if (dim == 16) NRK_REFINE_SV(4);
