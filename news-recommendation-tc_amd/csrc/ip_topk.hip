@@ -50,22 +50,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IP_KFAST = 128;   // largest k on the screen path
 constexpr int IP_KMAX = 2048;   // largest k at all (exact path above IP_KFAST)
-// screen tile: one LDS ring slot, one barrier (dev builds may try NRK_SCAN_TILE = 16384)
-#ifndef NRK_SCAN_TILE
-#define NRK_SCAN_TILE 8192
-#endif
-constexpr int SCAN_TILE = NRK_SCAN_TILE;
+// screen tile: one LDS ring slot, one barrier
+constexpr int SCAN_TILE = 8192;
 // dim 128 (BASELINE config 5): blocks per tile -- a 32-item block is already
 // 8 KB there; 4 blocks (32-KB tiles): one barrier / DMA wait per four blocks
 // and the next block's fragments read under the current block's MFMAs (see
 // ip_scan_kernel's PF2).  250k users x 5M items, one box (tools/scan128.py,
 // rows identical): 275.6 ms at 1 block, 254.3 at 2, 245.1 at 4
-#ifndef NRK_SCAN_TB128
-#define NRK_SCAN_TB128 4
-#endif
+constexpr int SCAN_TB128 = 4;
 // 32-item blocks per screen tile (one LDS ring slot, one barrier) at padded dim dp
 __host__ __device__ constexpr int scan_tb(int dp) {
-    return dp == 128 ? NRK_SCAN_TB128 : (64 * dp >= SCAN_TILE ? 1 : SCAN_TILE / (64 * dp));
+    return dp == 128 ? SCAN_TB128 : (64 * dp >= SCAN_TILE ? 1 : SCAN_TILE / (64 * dp));
 }
 constexpr int IP_SEL = 512;     // appended maxima >= theta_lb held by the select
 constexpr int IP_BQ = 288;      // largest band (k = 128); the refine holds SV + 32 entries
@@ -104,6 +99,11 @@ static inline size_t catalog_body_bytes(int64_t n_items, int dp) {
 // one 16 dp-B run per half-block instead of half of every 128-B line of the
 // fragment-ordered body
 __host__ __device__ static inline bool catalog_has_hb(int dp) { return dp <= 64; }
+// catalog row of item r (0..15) of half-block q: the rows one lane's 16 MFMA
+// accumulators hold (half h = q & 1 of block q >> 1)
+__host__ __device__ static inline int64_t hb_row(uint32_t q, int r) {
+    return (int64_t)(q >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (q & 1);
+}
 __host__ __device__ static inline size_t catalog_hb_offset(int64_t n_items, int dp) {
     return (size_t)n_blocks_of(n_items) * 64u * (size_t)dp + CATALOG_HDR;
 }
@@ -303,9 +303,10 @@ __device__ __forceinline__ void top_insert(float (&t)[MT], float v) {
     t[0] = fmaxf(t[0], v);
 }
 
-// dev-only phase stamps of ip_scan_kernel (make dev DEVFLAGS=-DNRK_SCAN_STAMP=1,
-// read by nrk_dev_scan_stamps): waves 0 and NW / 2 of each workgroup (the
-// first of each stagger half), shader cycles per phase
+// dev-only phase stamps of the scan kernels (make dev DEVFLAGS=-DNRK_SCAN_STAMP=1,
+// read by nrk_dev_scan_stamps), shader cycles per phase: ip_scan_kernel's
+// waves 0 and NW / 2 of each workgroup (the first of each stagger half),
+// ip_scan_ws_kernel's waves 0 and SCAN_WS_STAMPW (an MFMA and a book wave)
 #ifndef NRK_SCAN_STAMP
 #define NRK_SCAN_STAMP 0
 #endif
@@ -358,6 +359,7 @@ __device__ __forceinline__ uint32_t first_set_block8(const uint64_t (&am)[8]) {
 }
 #if NRK_SCAN_STAMP
 __device__ unsigned long long scan_stamps[1024 * 16];
+constexpr int SCAN_WS_STAMPW = 4;  // ip_scan_ws_kernel: the book wave stamped beside wave 0
 #define SC_STAMP(k)                                           \
     do {                                                      \
         const uint64_t t_now_ = __builtin_readcyclecounter(); \
@@ -472,13 +474,85 @@ __device__ __forceinline__ void scan_user_setup(const float* __restrict__ users,
 // Per-user screen record (uinfo): theta_lb (scaled), eps (scaled), the
 // exact power-of-two scale scl = su * catalog scale, eps (unscaled).
 //
+// ---- helpers shared by ip_scan_kernel and ip_scan_ws_kernel ----
+// The cut of one user from its list: lb = the pair's smaller (jk + 1)-th
+// largest maximum (t_last = the lane's), tau below the exact lb - 2 eps:
+// c = RN(lb - 2 eps) is within half an ulp of it, |c| 2^-22 >= 2 ulp(c) covers
+// that and the fma's own rounding, - 2^-120 covers c = 0 (absorbed for
+// |c| > 2^-96); lb = -inf gives -FLT_MAX (a -inf maximum, rows past the
+// catalog end, is never appended)
+__device__ __forceinline__ float scan_tau(float t_last, float eps_s, bool live) {
+    const float lb = pair_min32(t_last);
+    const float c = lb - 2.0f * eps_s;
+    const float tv = fmaxf(__builtin_fmaf(fabsf(c), -0x1p-22f, c) - 0x1p-120f, -FLT_MAX);
+    return live ? tv : INFINITY;
+}
+
+// One append entry stored from the lanes of m only, at base (wave-uniform) +
+// off bytes, without a branch: the compiler's form (s_and_saveexec,
+// s_cbranch_execz, store, s_or exec per half-block) cost ~55 cycles per
+// (group, block) in the phase stamps, mostly the branch; a store with no lane
+// left is a no-op
+__device__ __forceinline__ void app_store_masked(uint64_t m, const uint2* base, uint32_t off, uint2 v) {
+    const uint64_t d = ((uint64_t)v.y << 32) | v.x;
+    uint64_t sv;
+    asm volatile(
+        "s_and_saveexec_b64 %0, %1\n\t"
+        "global_store_dwordx2 %2, %3, %4\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(sv)
+        : "s"(m), "v"(off), "v"(d), "s"(base)
+        : "memory", "scc");  // s_and_saveexec writes SCC
+}
+
+// The ring is filled by LDS-DMA (global_load_lds_dwordx4: one 1-KB piece per
+// wave-instruction, no VGPR staging): dma_piece(piece_src(...), dst).
+// piece_src: this lane's 16 B of the piece at byte offset off of the packed
+// body; a piece past the body re-loads the last one (keeps the per-wave vmcnt
+// accounting uniform, the data is never used).  The callers clamp the tile to
+// the catalog's last one before they form the 32-bit offset (their prefetches
+// run past the range), so a body just under 2 GiB (ip_check's limit) cannot
+// wrap it negative.
+__device__ __forceinline__ const uint8_t* piece_src(const uint8_t* catalog, uint32_t off, int body_bytes, int lane) {
+    off = off < (uint32_t)body_bytes ? off : (uint32_t)body_bytes - 1024u;
+    return catalog + off + lane * 16;
+}
+__device__ __forceinline__ void dma_piece(const uint8_t* src, uint8_t* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+// DS = 2: block b + 1's fragments (at LDS address base) are read while block
+// b's MFMAs run -- the wait for block b's data and the issue of block b + 1's
+// reads are one asm statement whose operands tie both register sets, so
+// nothing reads (or copies) a fragment before its wait.  (All fragment reads
+// and their waits are inline asm: hipcc's waitcnt pass would otherwise drain
+// the in-flight LDS-DMA in front of a compiler-visible LDS access.)
+__device__ __forceinline__ void pf_issue(uint32_t base, u32x4 (&af)[2]) {
+    asm volatile("ds_read_b128 %0, %2 offset:0\n\tds_read_b128 %1, %2 offset:1024"
+                 : "=&v"(af[0]), "=&v"(af[1])
+                 : "v"(base)
+                 : "memory");
+}
+__device__ __forceinline__ void pf_wait_issue(u32x4 (&cur)[2], uint32_t base, u32x4 (&nxt)[2]) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %0, %4 offset:0\n\tds_read_b128 %1, %4 offset:1024"
+                 : "=&v"(nxt[0]), "=&v"(nxt[1]), "+v"(cur[0]), "+v"(cur[1])
+                 : "v"(base)
+                 : "memory");
+}
+__device__ __forceinline__ void pf_wait(u32x4 (&cur)[2]) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1])::"memory");
+}
+
 // The scan (every shape but the warp-specialized one below): workgroup ub
 // takes user block ub -- NW waves x UG x 32 users -- over the tiles
 // [tile_lo, tile_hi); the waves share one NSL-slot LDS ring of catalog tiles
 // (8 KB, or one 16-KB block at dim 256).  Per tile every wave reads the tile's
 // A fragments and runs TB x DS x UG MFMAs.
-template <int DP, int NW, int NSL, int UG, int MT, int WPE>
-__global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
+// 2 waves per SIMD everywhere: at 4 (128 VGPRs) the dim-16 / dim-64 k <= 32
+// and the dim-32 k <= 64 variants spilled 42-96 VGPRs to scratch.
+template <int DP, int NW, int NSL, int UG, int MT>
+__global__ __launch_bounds__(NW * 64, 2) void ip_scan_kernel(
     const float* __restrict__ users, int n_users, const uint8_t* __restrict__ catalog, int n_items, int dim, int k,
     int m2, uint2* __restrict__ app, int32_t* __restrict__ acnt, float4* __restrict__ uinfo, int tile_lo,
     int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m) {
@@ -542,34 +616,15 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
         lim[g] = pos[g] + (uint32_t)m2 - 1u;
     }
     auto slot = [&](uint32_t x, int g) -> uint32_t { return min(x, lim[g]); };
-    // the store from the lanes with a set only, without a branch: the
-    // compiler's form (s_and_saveexec, s_cbranch_execz, store, s_or exec per
-    // half-block) cost ~55 cycles per (group, block) in the phase stamps,
-    // mostly the branch; a store with no lane left is a no-op
-    auto app_store_if = [&](uint64_t m, uint32_t e, uint2 v) {
-        const uint32_t off = e << 3;
-        const uint64_t d = ((uint64_t)v.y << 32) | v.x;
-        uint64_t sv;
-        asm volatile(
-            "s_and_saveexec_b64 %0, %1\n\t"
-            "global_store_dwordx2 %2, %3, %4\n\t"
-            "s_mov_b64 exec, %0"
-            : "=&s"(sv)
-            : "s"(m), "v"(off), "v"(d), "s"(wapp)
-            : "memory", "scc");  // s_and_saveexec writes SCC
-    };
+    // entry e of the wave's lists, from the lanes of m (app_store_masked)
+    auto app_store_if = [&](uint64_t m, uint32_t e, uint2 v) { app_store_masked(m, wapp, e << 3, v); };
 
     const uint32_t lds_base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)(smem);
     const int body_bytes = nblk * BLOCK_BYTES;
     const int tail_blk = n_items >> 5;  // first block holding a row >= n_items
-    // Tile t -> ring slot t % NSL by LDS-DMA (global_load_lds_dwordx4: one
-    // 1-KB piece per wave-instruction, no VGPR staging); tiles past the end
-    // re-load the last piece (keeps the per-wave vmcnt accounting uniform,
-    // the data is never used).
-    // The prefetches run past the range (the main loop NSL - 1 tiles, the
-    // pre-pass (NSL - 1) * pstride): the tile is clamped to the catalog's last
-    // one before the 32-bit offset is formed, so a body just under 2 GiB
-    // (ip_check's limit) cannot wrap it negative.
+    // Tile t -> ring slot t % NSL, LPT pieces per wave (dma_piece).  The
+    // prefetches run past the range (the main loop NSL - 1 tiles, the pre-pass
+    // (NSL - 1) * pstride), hence the clamp to the catalog's last tile.
     const int last_tile = (nblk - 1) / TB;
     auto issue_tile = [&](int tt, int sl) {
         uint8_t* slot = smem + sl * TILE_BYTES;
@@ -577,21 +632,20 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
 #pragma unroll
         for (int p = 0; p < LPT; ++p) {
             const int piece = p * NW + wave;
-            uint32_t off = ttc * (uint32_t)TILE_BYTES + (uint32_t)piece * 1024u;
-            off = off < (uint32_t)body_bytes ? off : (uint32_t)body_bytes - 1024u;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(catalog + off + lane * 16),
-                (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, 0, 0);
+            dma_piece(piece_src(catalog, ttc * (uint32_t)TILE_BYTES + (uint32_t)piece * 1024u, body_bytes, lane),
+                      slot + piece * 1024);
         }
     };
     const uint32_t lds0 = lds_base + lane * 16;
+    // LDS address of this lane's fragments of block b of ring slot sl
+    auto frag_base = [&](int sl, int b) -> uint32_t { return lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024); };
     // all fragment reads and their wait in inline asm: hipcc's waitcnt pass
     // would otherwise drain the in-flight LDS-DMA (the ring prefetch) in
     // front of a compiler-visible LDS access, and a separate wait statement
     // would let the compiler copy an output before the data landed.
     // One block's DS fragments, one LDS round trip per block:
     auto read_block = [&](int sl, int b, u32x4 (&af)[DS]) {
-        const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
+        const uint32_t base = frag_base(sl, b);
         if constexpr (DS == 1) {
             asm volatile("ds_read_b128 %0, %1 offset:0\n\ts_waitcnt lgkmcnt(0)" : "=&v"(af[0]) : "v"(base) : "memory");
         } else {
@@ -603,35 +657,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
                              : "memory");
         }
     };
-    // DS = 2: block b + 1's fragments are read while block b's MFMAs run --
-    // the wait for block b's data and the issue of block b + 1's reads are one
-    // asm statement whose operands tie both register sets, so nothing reads
-    // (or copies) a fragment before its wait
+    // DS = 2: block b + 1's fragments are read while block b's MFMAs run
+    // (pf_issue / pf_wait_issue / pf_wait)
     constexpr bool PF = DS == 2;
-    auto pf_issue = [&](int sl, int b, u32x4 (&af)[DS]) {
-        const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
-        asm volatile("ds_read_b128 %0, %2 offset:0\n\tds_read_b128 %1, %2 offset:1024"
-                     : "=&v"(af[0]), "=&v"(af[1])
-                     : "v"(base)
-                     : "memory");
-    };
-    auto pf_wait_issue = [&](u32x4 (&cur)[DS], int sl, int b, u32x4 (&nxt)[DS]) {
-        const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %0, %4 offset:0\n\tds_read_b128 %1, %4 offset:1024"
-                     : "=&v"(nxt[0]), "=&v"(nxt[1]), "+v"(cur[0]), "+v"(cur[1])
-                     : "v"(base)
-                     : "memory");
-    };
-    auto pf_wait = [&](u32x4 (&cur)[DS]) {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1])::"memory");
-    };
     // DS >= 4 with several blocks per tile (dims 64, 128): two fragment sets
     // by block parity -- block b + 1's DS reads are issued right after block
     // b's have landed, so they fly under block b's UG x DS MFMAs (one LDS
     // round trip per tile exposed instead of one per block)
     constexpr bool PF2 = DS >= 4 && TB >= 2;
     auto blk_issue = [&](int sl, int b, u32x4 (&af)[DS]) {
-        const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
+        const uint32_t base = frag_base(sl, b);
 #pragma unroll
         for (int s2 = 0; s2 < DS; s2 += 4)
             asm volatile(
@@ -665,14 +700,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
     auto tile = [&](int tt, int sl, auto mask_c, float (&mx)[UG][TB]) __attribute__((always_inline)) {
         constexpr bool MASK = decltype(mask_c)::value;
         u32x4 afp[DS];
-        if constexpr (PF) pf_issue(sl, 0, afp);
+        if constexpr (PF) pf_issue(frag_base(sl, 0), afp);
         auto red = [&](const f32x16& a, int bb, int gg) __attribute__((always_inline)) {
             float x[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 x[r] = a[r];
                 if constexpr (MASK) {
-                    const int row = (tt * TB + bb) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int row = (tt * TB + bb) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;  // hb_row, 32-bit
                     if (row >= n_items) x[r] = -INFINITY;
                 }
             }
@@ -695,7 +730,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
                 for (int s = 0; s < DS; ++s) afb[s] = fb2[b & 1][s];
             } else if constexpr (PF) {
                 u32x4 afn[DS];
-                if constexpr (b + 1 < TB) pf_wait_issue(afp, sl, b + 1, afn);
+                if constexpr (b + 1 < TB) pf_wait_issue(afp, frag_base(sl, b + 1), afn);
                 else pf_wait(afp);
 #pragma unroll
                 for (int s = 0; s < DS; ++s) afb[s] = afp[s];
@@ -737,16 +772,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
             red(acc[j % NACC], j / UG, j % UG);
         });
     };
-    // tau below the exact lb - 2 eps: c = RN(lb - 2 eps) is within half an ulp
-    // of it, |c| 2^-22 >= 2 ulp(c) covers that and the fma's own rounding,
-    // - 2^-120 covers c = 0 (absorbed for |c| > 2^-96); lb = -inf gives
-    // -FLT_MAX (a -inf maximum, rows past the catalog end, is never appended)
-    auto retau = [&](int g) {
-        const float lb = pair_min32(t[g][MT - 1]);
-        const float c = lb - 2.0f * eps_s[g];
-        const float tv = fmaxf(__builtin_fmaf(fabsf(c), -0x1p-22f, c) - 0x1p-120f, -FLT_MAX);
-        tau[g] = live[g] ? tv : INFINITY;
-    };
+    auto retau = [&](int g) { tau[g] = scan_tau(t[g][MT - 1], eps_s[g], live[g]); };
     auto book = [&](int tt, const float (&mx)[UG][TB], bool ins_ok) __attribute__((always_inline)) {
         // the lane's largest max of the tile, per user group
         float vt[UG];
@@ -841,8 +867,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
     // MFMAs, so one half's bookkeeping VALU runs beside the other half's
     // MFMAs.  The book order per wave is unchanged (tile t's appends use the
     // tau left by tile t - 1's inserts), so the lists are identical.
-    // (WPE = 4: two workgroups per CU already interleave on every SIMD)
-    const bool late = WPE == 2 && __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
+    const bool late = __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
     float mx[UG][TB];  // the LATE half keeps a tile's maxima across the barrier
     int ptt = -1;
     bool pins = true;
@@ -953,7 +978,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
 }
 
 // Warp-specialized scan (WS, round 5; D = 32, k <= 32: config 2 and every
-// config-4 shard): the one-pass screen of ip_scan_seg -- same lists, taus,
+// config-4 shard): the one-pass screen of ip_scan_kernel -- same lists, taus,
 // append format and list bounds; the appended set differs only by the insert
 // period below -- with the work of a SIMD split by role.  12 waves, 1,024
 // users per workgroup, one workgroup per CU.  Waves 0-3 (one per SIMD, the
@@ -971,54 +996,31 @@ __global__ __launch_bounds__(NW * 64, WPE) void ip_scan_kernel(
 // lags), pre-pass tiles every tile.  LDS: the 4-tile ring (32 KB) + 2 TPS
 // maxima slots x 4 pairs x 4 blocks x 2 group quads x 64 lanes x 16 B (128 KB).
 // Config 2, one box: 5.08 vs 5.41 ms for ip_scan_kernel.
-#ifndef NRK_SCAN_WS
-#define NRK_SCAN_WS 1
-#endif
-#ifndef NRK_SCAN_WS_PRIO
-#define NRK_SCAN_WS_PRIO 2
-#endif
-#ifndef NRK_SCAN_WS_INSP
-#define NRK_SCAN_WS_INSP 8
-#endif
-#ifndef NRK_SCAN_WS_STAMPW
-#define NRK_SCAN_WS_STAMPW 4
-#endif
-#ifndef NRK_SCAN_WS_FLOOR
-#define NRK_SCAN_WS_FLOOR 0
-#endif
-#ifndef NRK_SCAN_WS_TPS
-#define NRK_SCAN_WS_TPS 2
-#endif
-// book waves per MFMA wave (1: 8-wave workgroups, 2: 12)
-#ifndef NRK_SCAN_WS_NB
-#define NRK_SCAN_WS_NB 2
-#endif
-constexpr bool SCAN_WS = NRK_SCAN_WS;
-constexpr int SCAN_WS_NB = NRK_SCAN_WS_NB;
-#ifndef NRK_SCAN_WS_SHARD_INSP
-#define NRK_SCAN_WS_SHARD_INSP 4
-#endif
-constexpr int SCAN_WS_INSP = NRK_SCAN_WS_INSP, SCAN_WS_SHARD_INSP = NRK_SCAN_WS_SHARD_INSP;
-static_assert((SCAN_WS_INSP & (SCAN_WS_INSP - 1)) == 0 && SCAN_WS_INSP >= 2 &&
-                  (SCAN_WS_SHARD_INSP & (SCAN_WS_SHARD_INSP - 1)) == 0 && SCAN_WS_SHARD_INSP >= 2,
+constexpr int SCAN_WS_NB = 2;     // book waves per MFMA wave: 12-wave workgroups
+constexpr int SCAN_WS_TPS = 2;    // tiles per barrier step
+constexpr int SCAN_WS_PRIO = 2;   // s_setprio of the MFMA waves
+// main-pass insert periods in tiles (one GPU / a catalog shard)
+constexpr int SCAN_WS_INSP = 8, SCAN_WS_SHARD_INSP = 4;
+static_assert((SCAN_WS_INSP & (SCAN_WS_INSP - 1)) == 0 && SCAN_WS_INSP >= SCAN_WS_TPS &&
+                  (SCAN_WS_SHARD_INSP & (SCAN_WS_SHARD_INSP - 1)) == 0 && SCAN_WS_SHARD_INSP >= SCAN_WS_TPS,
               "insert periods: powers of two >= the two tiles of a step");
-template <int DP, int NSL, int MT, int NB>
-__global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws_kernel(
+template <int DP, int NSL, int MT>
+__global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kernel(
     const float* __restrict__ users, int n_users, const uint8_t* __restrict__ catalog, int n_items, int dim, int k,
     int m2, uint2* __restrict__ app, int32_t* __restrict__ acnt, float4* __restrict__ uinfo, int tile_lo,
     int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m, int insp) {
-    constexpr int NPW = 4, UG = 8, UGB = UG / NB, DS = DP / 16;
+    constexpr int NPW = 4, UG = 8, NB = SCAN_WS_NB, UGB = UG / NB, DS = DP / 16;
     constexpr int BLOCK_BYTES = 64 * DP;
     constexpr int TB = scan_tb(DP);
     constexpr int TILE_BYTES = TB * BLOCK_BYTES;
     constexpr int NPC = TILE_BYTES / 1024;  // 1-KB pieces per tile: waves 0 .. NPC - 1 load one each
-    static_assert(TB == 4 && DS == 2 && NPC == 8 && (NB == 1 || NB == 2), "WS scan: 8-KB tiles of four blocks at DP = 32");
+    static_assert(TB == 4 && DS == 2 && NPC == 8 && UGB == 4, "WS scan: 8-KB tiles of four blocks at DP = 32");
     // TPS tiles per barrier step: at step p the MFMA waves run tiles TPS p ..
     // TPS p + TPS - 1 and the book waves book step p - 1's.  Maxima slot:
     // [pair][block][group quad][lane] x 4 floats (the quad's groups); 2 TPS
     // slots.  Only the MFMA waves load the ring (LPW pieces per tile each,
     // DAHEAD steps ahead), so the book waves' appends never gate a barrier.
-    constexpr int TPS = NRK_SCAN_WS_TPS, NMX = 2 * TPS, LPW = NPC / NPW, DAHEAD = NSL / TPS - 1;
+    constexpr int TPS = SCAN_WS_TPS, NMX = 2 * TPS, LPW = NPC / NPW, DAHEAD = NSL / TPS - 1;
     static_assert(NSL % TPS == 0 && DAHEAD >= 1, "ring of whole steps, one step ahead at least");
     constexpr int MXP = TB * 2 * 1024, MXS = NPW * MXP;
     __shared__ __attribute__((aligned(16))) uint8_t smem[NSL * TILE_BYTES];
@@ -1036,7 +1038,7 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     uint64_t sstp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_prev = __builtin_readcyclecounter();
     auto stamp_out = [&]() {
-        if ((threadIdx.x == 0 || threadIdx.x == NRK_SCAN_WS_STAMPW * 64) && blockIdx.x < 1024)
+        if ((threadIdx.x == 0 || threadIdx.x == SCAN_WS_STAMPW * 64) && blockIdx.x < 1024)
             for (int c = 0; c < 8; ++c) scan_stamps[blockIdx.x * 16 + (threadIdx.x ? 8 : 0) + c] = sstp[c];
     };
 #endif
@@ -1055,18 +1057,15 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     const int tail_blk = n_items >> 5;
     const int full_tiles = tail_blk / TB;
     const int last_tile = (nblk - 1) / TB;
-    // MFMA wave wv loads pieces LPW wv .. LPW wv + LPW - 1 of every tile (see
-    // ip_scan_seg's issue_tile)
+    // MFMA wave wv loads pieces LPW wv .. LPW wv + LPW - 1 of every tile
+    // (dma_piece; the tile clamped as in ip_scan_kernel's issue_tile)
     auto issue_tile = [&](int tt, int sl) {
         const uint32_t ttc = (uint32_t)min(tt, last_tile);
 #pragma unroll
         for (int c = 0; c < LPW; ++c) {
             const int piece = wv * LPW + c;
-            uint32_t off = ttc * (uint32_t)TILE_BYTES + (uint32_t)piece * 1024u;
-            off = off < (uint32_t)body_bytes ? off : (uint32_t)body_bytes - 1024u;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(catalog + off + lane * 16),
-                (__attribute__((address_space(3))) void*)(smem + sl * TILE_BYTES + piece * 1024), 16, 0, 0);
+            dma_piece(piece_src(catalog, ttc * (uint32_t)TILE_BYTES + (uint32_t)piece * 1024u, body_bytes, lane),
+                      smem + sl * TILE_BYTES + piece * 1024);
         }
     };
     auto issue_step = [&](int p) {  // the TPS tiles of step p (past the end: dummies, uniform vmcnt)
@@ -1096,29 +1095,12 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
             scan_user_setup<DS>(users, n_users, dim, ubase + g * 32 + q, h, vmax, dvmax, sv_scale, ufrag[g], eps, scl,
                                 live);
         }
-#if NRK_SCAN_WS_PRIO
-        __builtin_amdgcn_s_setprio(NRK_SCAN_WS_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(SCAN_WS_PRIO);
         const uint32_t lds0 = lds_base + lane * 16;
-        auto pf_issue = [&](int sl, int b, u32x4 (&af)[DS]) {
-            const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
-            asm volatile("ds_read_b128 %0, %2 offset:0\n\tds_read_b128 %1, %2 offset:1024"
-                         : "=&v"(af[0]), "=&v"(af[1])
-                         : "v"(base)
-                         : "memory");
-        };
-        auto pf_wait_issue = [&](u32x4 (&cur)[DS], int sl, int b, u32x4 (&nxt)[DS]) {
-            const uint32_t base = lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %0, %4 offset:0\n\tds_read_b128 %1, %4 offset:1024"
-                         : "=&v"(nxt[0]), "=&v"(nxt[1]), "+v"(cur[0]), "+v"(cur[1])
-                         : "v"(base)
-                         : "memory");
-        };
-        auto pf_wait = [&](u32x4 (&cur)[DS]) {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1])::"memory");
-        };
+        // LDS address of this lane's fragments of block b of ring slot sl
+        auto frag_base = [&](int sl, int b) -> uint32_t { return lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024); };
         // tile tt in ring slot sl -> the half-block maxima, written to maxima
-        // slot ms block by block (software pipeline of ip_scan_seg's tile():
+        // slot ms block by block (software pipeline of ip_scan_kernel's tile():
         // step j = (block, group) issues its MFMAs while step j - 2 reduces;
         // block b's maxima are complete after step 8 b + 9)
         // NT tiles (tt[t] in ring slot sl[t], maxima to slot ms[t]) as one
@@ -1169,11 +1151,11 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
             f32x16 acc[2];
             float pm[2][5];  // partial maxima by step parity
             u32x4 afp[DS], afb[DS];
-            pf_issue(slb(0), 0, afp);
+            pf_issue(frag_base(slb(0), 0), afp);
             static_for<NBK>([&](auto bc) {
                 constexpr int bb = decltype(bc)::value;
                 u32x4 afn[DS];
-                if constexpr (bb + 1 < NBK) pf_wait_issue(afp, slb(bb + 1), (bb + 1) % TB, afn);
+                if constexpr (bb + 1 < NBK) pf_wait_issue(afp, frag_base(slb(bb + 1), (bb + 1) % TB), afn);
                 else pf_wait(afp);
 #pragma unroll
                 for (int s = 0; s < DS; ++s) afb[s] = afp[s];
@@ -1243,7 +1225,10 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     }
 
     // --------------------------------------------------------- book waves --
-    // book wave wv books groups [gb, gb + UGB) of pair pw
+    // book wave wv books groups [gb, gb + UGB) of pair pw.  Their start below
+    // and their end (counts, list bound, shard bounds) at the bottom are
+    // ip_scan_kernel's, copied: either as a shared function changed the
+    // register allocation of both kernels, so a fix there goes to both copies
     const int gb = ((wv - NPW) / NPW) * UGB;
     float eps_s[UGB], tau[UGB];
     float t[UGB][MT];
@@ -1270,23 +1255,9 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
 #pragma unroll
     for (int g = 0; g < UGB; ++g) cnt[g] = 0u;
     auto app_store_if = [&](uint64_t m, int g, uint32_t e, uint2 v) {
-        const uint32_t off = (min(e, (uint32_t)m2 - 1u) << 3) + off0;
-        const uint64_t d = ((uint64_t)v.y << 32) | v.x;
-        uint64_t sv;
-        asm volatile(
-            "s_and_saveexec_b64 %0, %1\n\t"
-            "global_store_dwordx2 %2, %3, %4\n\t"
-            "s_mov_b64 exec, %0"
-            : "=&s"(sv)
-            : "s"(m), "v"(off), "v"(d), "s"(wapp + (size_t)g * gstride)
-            : "memory", "scc");
+        app_store_masked(m, wapp + (size_t)g * gstride, (min(e, (uint32_t)m2 - 1u) << 3) + off0, v);
     };
-    auto retau = [&](int g) {
-        const float lb = pair_min32(t[g][MT - 1]);
-        const float c = lb - 2.0f * eps_s[g];
-        const float tv = fmaxf(__builtin_fmaf(fabsf(c), -0x1p-22f, c) - 0x1p-120f, -FLT_MAX);
-        tau[g] = live[g] ? tv : INFINITY;
-    };
+    auto retau = [&](int g) { tau[g] = scan_tau(t[g][MT - 1], eps_s[g], live[g]); };
     int next_s = n_pre > 0 ? tile_lo : INT_MAX, left_s = n_pre;
 #if NRK_SCAN_STAMP
     t_prev = __builtin_readcyclecounter();
@@ -1295,24 +1266,12 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     // r[b][c]: block b's maxima of group quad c of this wave
     f32x4 rr[TPS][TB][UGB / 4];
     auto read_issue = [&](int t, uint32_t a) {
-        if constexpr (NB == 2) {
-            asm volatile(
-                "ds_read_b128 %0, %4 offset:0\n\tds_read_b128 %1, %4 offset:2048\n\t"
-                "ds_read_b128 %2, %4 offset:4096\n\tds_read_b128 %3, %4 offset:6144"
-                : "=&v"(rr[t][0][0]), "=&v"(rr[t][1][0]), "=&v"(rr[t][2][0]), "=&v"(rr[t][3][0])
-                : "v"(a)
-                : "memory");
-        } else {
-            asm volatile(
-                "ds_read_b128 %0, %8 offset:0\n\tds_read_b128 %1, %8 offset:1024\n\t"
-                "ds_read_b128 %2, %8 offset:2048\n\tds_read_b128 %3, %8 offset:3072\n\t"
-                "ds_read_b128 %4, %8 offset:4096\n\tds_read_b128 %5, %8 offset:5120\n\t"
-                "ds_read_b128 %6, %8 offset:6144\n\tds_read_b128 %7, %8 offset:7168"
-                : "=&v"(rr[t][0][0]), "=&v"(rr[t][0][1]), "=&v"(rr[t][1][0]), "=&v"(rr[t][1][1]),
-                  "=&v"(rr[t][2][0]), "=&v"(rr[t][2][1]), "=&v"(rr[t][3][0]), "=&v"(rr[t][3][1])
-                : "v"(a)
-                : "memory");
-        }
+        asm volatile(
+            "ds_read_b128 %0, %4 offset:0\n\tds_read_b128 %1, %4 offset:2048\n\t"
+            "ds_read_b128 %2, %4 offset:4096\n\tds_read_b128 %3, %4 offset:6144"
+            : "=&v"(rr[t][0][0]), "=&v"(rr[t][1][0]), "=&v"(rr[t][2][0]), "=&v"(rr[t][3][0])
+            : "v"(a)
+            : "memory");
     };
     // tile t's reads landed with LEFT later reads still in flight (LDS reads
     // return in order, and every step issues the reads of all its TPS tiles,
@@ -1322,18 +1281,10 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     auto read_wait = [&](int t, auto left_c) __attribute__((always_inline)) {
         constexpr int LEFT = decltype(left_c)::value;
         auto& r = rr[t];
-        if constexpr (NB == 2) {
-            asm volatile("s_waitcnt lgkmcnt(%4)"
-                         : "+v"(r[0][0]), "+v"(r[1][0]), "+v"(r[2][0]), "+v"(r[3][0])
-                         : "n"(LEFT)
-                         : "memory");
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(%8)"
-                         : "+v"(r[0][0]), "+v"(r[0][1]), "+v"(r[1][0]), "+v"(r[1][1]), "+v"(r[2][0]), "+v"(r[2][1]),
-                           "+v"(r[3][0]), "+v"(r[3][1])
-                         : "n"(LEFT)
-                         : "memory");
-        }
+        asm volatile("s_waitcnt lgkmcnt(%4)"
+                     : "+v"(r[0][0]), "+v"(r[1][0]), "+v"(r[2][0]), "+v"(r[3][0])
+                     : "n"(LEFT)
+                     : "memory");
     };
     // The appends of the NBK = TPS TB consecutive blocks of a step for group g:
     // every half-block maximum >= tau is one entry (value, half-block id), in
@@ -1416,7 +1367,7 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
     };
     constexpr int L1 = TB * (UGB / 4);  // maxima reads per tile
     // main-pass inserts every insp tiles (a power of two >= TPS; the host's
-    // choice, see launch_scan_v)
+    // choice, see launch_scan)
     float vtp[UGB];  // the largest tile maximum since the last insert, per group (-inf: none)
 #pragma unroll
     for (int g = 0; g < UGB; ++g) vtp[g] = -INFINITY;
@@ -1430,10 +1381,6 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
         sync();
         SC_STAMP(0);
         step_reads(p1);
-#if NRK_SCAN_WS_FLOOR  // dev timing floor: the book waves only read the maxima
-        read_wait(TPS - 1, std::integral_constant<int, 0>{});
-        if (rr[TPS - 1][0][0][0] != 12345.0f) continue;
-#endif
         static_for<TPS>([&](auto tc) {
             constexpr int T = decltype(tc)::value;
             read_wait(T, std::integral_constant<int, (TPS - 1 - T) * L1>{});  // later tiles' reads stay in flight
@@ -1457,9 +1404,6 @@ __global__ __launch_bounds__(64 * 4 * (1 + NB), NB == 1 ? 2 : 1) void ip_scan_ws
         const int j0 = TPS * p1;
         static_for<TPS>([&](auto tc) { read_wait(decltype(tc)::value, std::integral_constant<int, 0>{}); });
         SC_STAMP(1);
-#if NRK_SCAN_WS_FLOOR
-        if (rr[TPS - 1][0][0][0] != 12345.0f) continue;
-#endif
         if (p1 == PA) {  // the first main-pass tile is in this step: tau from the pre-pass lists
             static_for<TPS>([&](auto tc) {
                 constexpr int T = decltype(tc)::value;
@@ -1684,11 +1628,8 @@ __device__ __forceinline__ uint32_t lds_select(uint32_t* __restrict__ row, int c
 // or the queued ones run after the first finish (a second, thinner wave of
 // work).  Their ~106 SGPRs admit 6 4-wave workgroups per CU, not 8
 // (MI355X_MICROARCH.md: floor(800 / (ceil(sgpr / 16) 16 + 16)); the
-// occupancy API says 7).  Dev A/B: -DNRK_SH_WG=8 (the round-5 grid).
-#ifndef NRK_SH_WG
-#define NRK_SH_WG 6
-#endif
-constexpr int SH_WG_PER_CU = NRK_SH_WG;
+// occupancy API says 7); the round-5 grid was 8.
+constexpr int SH_WG_PER_CU = 6;
 constexpr int SH_ENT = 4;  // entries per lane per load batch
 
 __device__ __forceinline__ void sh_load(const uint2* s0, const uint2* s1, int a0, int n, int b0, int lane,
@@ -1850,18 +1791,29 @@ __device__ __forceinline__ double exact_dot(const float* __restrict__ a, const f
     return s + 0.0;
 }
 
+// One push into a wave's krow ring (the rows, or codes for them, that passed
+// the prefilter and await an exact round): the lanes with keep append v in
+// lane order from fill position kc; returns the new fill position
+__device__ __forceinline__ int ring_push(int32_t* ring, int kc, int lane, bool keep, int32_t v) {
+    const unsigned long long bal = __ballot(keep);
+    if (keep) ring[(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = v;
+    kc += __popcll(bal);
+    wave_sync_lds();
+    return kc;
+}
+
 // DS4 = dim / 4 when the candidate rows are staged through LDS (dim 16, 32,
 // 64): every 64-item round loads the rows with whole-row coalesced float4
 // pieces (64 / DS4 rows per instruction) into a padded per-wave LDS stage,
 // then each lane sums its own row sequentially (the oracle's order).
 // DS4 = 0: the generic per-lane gather.  SV = exact survivors held per user
-// (SV / 64 per lane in the final sort).
-// the exact rounds' rows read per lane (dims <= 32) instead of staged
-#ifndef NRK_REFINE_DIRECT
-#define NRK_REFINE_DIRECT 1
-#endif
-constexpr bool REFINE_DIRECT = NRK_REFINE_DIRECT;
-// waves per SIMD the refine's registers are sized for (dim 64's staged
+// (SV / 64 per lane in the final sort).  The body is three phases (banners
+// 1-3 below): band compaction, prefilter + exact rounds, survivor sort + emit.
+// Dims 16 and 32 (DS4 <= 8) read the exact rounds' rows per lane instead of
+// staging them, and their prefilter loads a half-block's contiguous run with
+// one wave load, DS4 / 2 lanes per item (LANES; a lane per item reads four
+// 16-B pieces 64 B apart: 32 cache lines per load instruction instead of 8).
+// REFINE_WPE: waves per SIMD the refine's registers are sized for (dim 64's staged
 // rounds take 2, the generic dims 4).  Round 6: two prefilter rounds in
 // flight (three register slots rotated by unrolling) at 3 waves per SIMD
 // measured slower than one round ahead at 4: finish 0.961-0.966 vs
@@ -1869,23 +1821,12 @@ constexpr bool REFINE_DIRECT = NRK_REFINE_DIRECT;
 // and the direct exact dot to two half-rows: dim 32 needs 80 VGPRs instead of
 // 128, and finish went 0.871 -> 0.776 ms at 4 / 0.772 at 6 waves per SIMD
 // (one box, two runs each)
-#ifndef NRK_REFINE_WPE
-#define NRK_REFINE_WPE 6
-#endif
-// dims 16 and 32: the prefilter loads a half-block's contiguous run with one
-// wave load, DS4 / 2 lanes per item (0: a lane per item, four 16-B pieces 64 B
-// apart: 32 cache lines per load instruction instead of 8)
-#ifndef NRK_REFINE_LANES
-#define NRK_REFINE_LANES 1
-#endif
-// callers without out_exact sort up to 64 survivors on one u64 key
-#ifndef NRK_REFINE_KEY64
-#define NRK_REFINE_KEY64 1
-#endif
-// FK: out_e == nullptr, so the final order may be taken on the fp32 score
-// (with the exact sort behind it whenever two fp32 scores tie)
+constexpr int REFINE_WPE = 6;
+// FK: out_e == nullptr, so up to 64 survivors are sorted on one u64 key: the
+// final order taken on the fp32 score (with the exact sort behind it whenever
+// two fp32 scores tie)
 template <int DS4, int SV, bool FK>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ? 2 : DS4 == 0 ? 4 : NRK_REFINE_WPE))) void ip_refine_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ? 2 : DS4 == 0 ? 4 : REFINE_WPE))) void ip_refine_kernel(
     const float* __restrict__ users, int64_t n_users, const float* __restrict__ items,
     const uint8_t* __restrict__ catalog, int64_t n_items, int dim, int k, int64_t row_offset,
     const uint2* __restrict__ cand, int bandcap, const int32_t* __restrict__ cand_cnt,
@@ -1989,7 +1930,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         }
         pcut = ce.x * (su * hdr->scale);
     }
-    // (a) compact the band into LDS (list order kept; sources in rank order)
+    // ---- 1. band compaction into LDS (list order kept; sources in rank order)
     int nband = 0;
     auto take_one = [&](uint2 ent, int e, int cnt) {
         const bool kp = e < cnt && (!pre || __uint_as_float(ent.x) >= pcut);
@@ -2025,6 +1966,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         take(bd, nbd);
     }
     wave_sync_lds();
+    // ---- 2. prefilter + exact rounds: LANES (dims 16, 32), rows (dim 64) or
+    // generic; push() collects the survivors (exact score >= thr)
     const int nitem = nband * 16;
     int cnt = 0;
     auto push = [&](bool keep, double s, int32_t row) {
@@ -2041,7 +1984,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         // one exact round: the rows staged through LDS with whole-row
         // coalesced float4 pieces, each lane summing its own row sequentially
         // (the oracle's order).
-        constexpr bool LANES = NRK_REFINE_LANES && (DS4 == 4 || DS4 == 8);
+        constexpr bool LANES = DS4 == 4 || DS4 == 8;
         const uint8_t* hbc = catalog ? catalog + catalog_hb_offset(n_items, 4 * DS4) : nullptr;
         int kc = 0, ko = 0;  // ring fill / read positions (wave-uniform)
         // rows staged 32 at a time (half the LDS of a whole round: four
@@ -2054,13 +1997,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
                 if (rl >= 0) {
                     const uint32_t qv = bandq[wave][rl >> 4];
                     const int r = rl & 15;
-                    const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
+                    const int64_t rr = hb_row(qv, r);
                     rl = rr < n_items ? (int32_t)rr : -1;
                 }
             }
             double sd = 0.0;
             bool keep = false;
-            if constexpr (REFINE_DIRECT && DS4 <= 8) {
+            if constexpr (DS4 <= 8) {
                 // every lane reads its own row (one 128-B line at D = 32) and
                 // sums it: no LDS stage and no half-idle passes (config 2:
                 // finish 0.91 -> 0.87 ms).  D = 64 keeps the staged rounds
@@ -2209,11 +2152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
                         qn = group_q(g + 2 < ngrp ? g + 2 : g + 1);
                     }
                 }
-                const unsigned long long bal = __ballot(keep);
-                if (keep)
-                    krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = hb * 16 + (itl & 15);
-                kc += __popcll(bal);
-                wave_sync_lds();
+                kc = ring_push(krow[wave], kc, lane, keep, hb * 16 + (itl & 15));
                 // (B) exact rounds on full 64-row chunks
                 while (kc - ko >= WAVE) exact_round(WAVE);
             }
@@ -2230,7 +2169,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
             int64_t hoff = 0;
             auto item_row = [&](int base, uint32_t qv, int32_t& row, bool& inb) {
                 const int idx = base + lane, r = idx & 15;
-                const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
+                const int64_t rr = hb_row(qv, r);
                 inb = idx < nitem && rr < n_items;
                 row = inb ? (int32_t)rr : 0;
                 hoff = inb ? ((int64_t)qv * 16 + r) * (8 * DS4) : 0;
@@ -2278,10 +2217,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
                     pieces(row);
                     q1 = band_q(nb + WAVE < nitem ? nb + WAVE : nb);
                 }
-                const unsigned long long bal = __ballot(keep);
-                if (keep) krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = row_cur;
-                kc += __popcll(bal);
-                wave_sync_lds();
+                kc = ring_push(krow[wave], kc, lane, keep, row_cur);
                 // (B) exact rounds on full 64-row chunks
                 while (kc - ko >= WAVE) exact_round(WAVE);
             }
@@ -2323,7 +2259,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
             if (idx < nitem) {
                 const int bb = idx >> 4, r = idx & 15;
                 const uint32_t qv = bandq[wave][bb];
-                const int64_t rr = (int64_t)(qv >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (qv & 1);
+                const int64_t rr = hb_row(qv, r);
                 if (rr < n_items) row = (int32_t)rr;
                 keep = rr < n_items;
                 if (keep && pre) {
@@ -2343,6 +2279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
                     keep = acc >= pcut;
                 }
             }
+            // ring_push, written out: the call changes this variant's schedule
             const unsigned long long bal = __ballot(keep);
             if (keep) krow[wave][(kc + __popcll(bal & ((1ull << lane) - 1ull))) & (IP_KRING - 1)] = row;
             kc += __popcll(bal);
@@ -2356,7 +2293,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         return;
     }
     wave_sync_lds();
-    // survivors ordered (score desc, row asc); the first k are the output
+    // ---- 3. survivors ordered (score desc, row asc); the first k are the output
     auto emit = [&](const Cand* x, int ne) {
         for (int e = 0; e < ne; ++e) {
             const int idx = e * 64 + lane;
@@ -2372,7 +2309,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         // up to 64 survivors (nearly every user at config 2): one per lane, a
         // 64-wide sort -- 21 shuffle stages instead of the SV-wide sort's 28 x
         // SE (finish 1.27 -> 0.93 ms; rank counting over LDS broadcasts: 0.94)
-        if constexpr (FK && NRK_REFINE_KEY64) {
+        if constexpr (FK) {
             // nobody reads the exact score: sort the key (fp32 score's ordered
             // key, ~row), i.e. (fp32 score desc, row asc).  fp32 rounding is
             // monotone, so this is the exact order unless two neighbours among
@@ -3007,7 +2944,7 @@ struct IpWs {
     int32_t* slow_list;  // exact path: users with too many fp32 ties (count at ovf_count[1])
     int bandcap, m2;
     int blk_lo, blk_hi;  // block range screened (config-4 shards), set by the caller
-    float* bnd = nullptr;  // config-4 shard: the scan's per-user bounds (ip_scan_kernel's bnd)
+    float* bnd = nullptr;  // config-4 shard: the scan's per-user bounds (the scan kernels' bnd)
     int bnd_m = 0;
     size_t bytes;
 };
@@ -3083,7 +3020,7 @@ static inline int next_pow2(int x) {
     return p;
 }
 
-// compute units of the current device (the persistent grids, the FLAT scan)
+// compute units of the current device (the persistent grids)
 static int n_cus() {
     static const int n_cu = [] {
         int dev = 0, cu = 256;
@@ -3093,73 +3030,76 @@ static int n_cus() {
     return n_cu;
 }
 
-// scan variants: (DP, waves per workgroup, ring slots, user groups per wave,
-// register list length, waves per SIMD)
-// ring slots of the UG = 4 scan (config 2): 4 (one more tile in flight
-// than round 3's 3) since the bookkeeping got cheaper -- bench context, one
-// box, three pairs: scan 5.77 vs 5.80-5.86 ms
-constexpr int SCAN_NSL4 = 4;
-template <int DP, int NW, int NSL, int UG, int MT, int WPE>
+// The tile range of one scan launch and its list pre-pass: up to 64 tiles
+// spread over the range (+2.2% MFMA at config 2, +17% on a config-4 shard,
+// whose appends it cuts by 2/3)
+struct ScanRange {
+    int t_lo, t_hi, n_pre, pstride;
+};
+static ScanRange scan_range(int tb, int n_items, const IpWs& w) {
+    const int nblk = (n_items + 31) / 32;
+    ScanRange r;
+    r.t_lo = w.blk_lo / tb;
+    r.t_hi = (std::min(w.blk_hi, nblk) + tb - 1) / tb;
+    const int n = r.t_hi - r.t_lo;
+    const int pre_div = w.bnd != nullptr ? SCAN_SHARD_PRE_DIV : SCAN_PRE_DIV;  // a catalog shard's own
+    r.n_pre = n >= SCAN_PRE_MIN ? std::min(SCAN_PRE_MAX, n / pre_div) : 0;
+    r.pstride = r.n_pre > 0 ? n / r.n_pre : 1;
+    return r;
+}
+
+// ip_scan_kernel variants: (DP, waves per workgroup, ring slots, user groups
+// per wave, register list length)
+template <int DP, int NW, int NSL, int UG, int MT>
 static void launch_scan_v(const float* users, int n_users, const uint8_t* cat, int n_items, int dim, int k,
                           const IpWs& w, hipStream_t s) {
     const int per_wg = NW * 32 * UG;
-    constexpr int TB = scan_tb(DP);
-    const int nblk = (n_items + 31) / 32;
-    const int t_lo = w.blk_lo / TB, t_hi = (std::min(w.blk_hi, nblk) + TB - 1) / TB;
+    const ScanRange r = scan_range(scan_tb(DP), n_items, w);
     const unsigned grid = (unsigned)((n_users + per_wg - 1) / per_wg);
-    // the list pre-pass: up to 64 tiles spread over the range (+2.2% MFMA at
-    // config 2, +17% on a config-4 shard, whose appends it cuts by 2/3)
-    const int n = t_hi - t_lo;
-    const int pre_div = w.bnd != nullptr ? SCAN_SHARD_PRE_DIV : SCAN_PRE_DIV;  // a catalog shard's own
-    const int n_pre = n >= SCAN_PRE_MIN ? std::min(SCAN_PRE_MAX, n / pre_div) : 0;
-    const int pstride = n_pre > 0 ? n / n_pre : 1;
-    if constexpr (SCAN_WS && DP == 32 && MT == 16 && NW == 8 && UG == 4) {
-        // the warp-specialized form of this variant (same users per workgroup)
-        // a catalog shard (list bounds) inserts more often: its appended
-        // maxima are what the band pass reads
-        const int insp = w.bnd != nullptr ? SCAN_WS_SHARD_INSP : SCAN_WS_INSP;
-        ip_scan_ws_kernel<DP, NSL, MT, SCAN_WS_NB><<<grid, 256 * (1 + SCAN_WS_NB), 0, s>>>(
-            users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, t_lo, t_hi, n_pre, pstride, w.bnd,
-            w.bnd_m, insp);
-        return;
-    }
-    ip_scan_kernel<DP, NW, NSL, UG, MT, WPE><<<grid, NW * 64, 0, s>>>(
-        users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, t_lo, t_hi, n_pre, pstride, w.bnd,
-        w.bnd_m);
+    ip_scan_kernel<DP, NW, NSL, UG, MT><<<grid, NW * 64, 0, s>>>(
+        users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, r.t_lo, r.t_hi, r.n_pre, r.pstride,
+        w.bnd, w.bnd_m);
 }
 
+// ring slots of the D = 32, k <= 32 scan (config 2): 4 (one more tile in
+// flight than round 3's 3) since the bookkeeping got cheaper -- bench context,
+// one box, three pairs: scan 5.77 vs 5.80-5.86 ms
+constexpr int SCAN_NSL4 = 4;
 // ring slots of dim 128's 8-wave scan: 4 x 32 KB (tools/scan128.py, 250k x
 // 5M, one box, two pairs: 240.2-240.7 vs 241.6-242.8 ms at 3; rows identical)
-#ifndef NRK_SCAN128_NSL
-#define NRK_SCAN128_NSL 4
-#endif
+constexpr int SCAN128_NSL = 4;
 template <int DP, int MT>
 static void launch_scan(const float* users, int n_users, const uint8_t* cat, int n_items, int dim, int k,
                         const IpWs& w, hipStream_t s) {
-    constexpr int UG = (DP <= 128 && MT <= 32) ? 2 : 1;
-    // 2 waves per SIMD everywhere: at 4 (128 VGPRs) the dim-16 / dim-64
-    // k <= 32 and the dim-32 k <= 64 variants spilled 42-96 VGPRs to scratch
-    constexpr int WPE = 2;
     if constexpr (DP == 32 && MT == 16) {
-        // default at D = 32, k <= 32 (BASELINE config 2): 8 waves x 128 users
-        // (UG = 4) per workgroup at 2 waves / SIMD -- every LDS fragment read
-        // and tile barrier serves twice the MFMAs of the 64-user waves
-        // (round 3): config-2 screen 6.8-7.0 vs 7.0-7.2 ms
-        launch_scan_v<DP, 8, SCAN_NSL4, 4, MT, 2>(users, n_users, cat, n_items, dim, k, w, s);
-        return;
+        // D = 32, k <= 32 (BASELINE config 2 and its shards): the
+        // warp-specialized scan, 1,024 users per workgroup.  It replaced the
+        // 8 waves x 128 users (UG = 4) ip_scan_kernel variant of round 3
+        // (config-2 screen 6.8-7.0 vs 7.0-7.2 ms for the 64-user waves).
+        // A catalog shard (list bounds) inserts more often: its appended
+        // maxima are what the band pass reads
+        const int per_wg = 4 * 8 * 32;
+        const ScanRange r = scan_range(scan_tb(DP), n_items, w);
+        const unsigned grid = (unsigned)((n_users + per_wg - 1) / per_wg);
+        const int insp = w.bnd != nullptr ? SCAN_WS_SHARD_INSP : SCAN_WS_INSP;
+        ip_scan_ws_kernel<DP, SCAN_NSL4, MT><<<grid, 256 * (1 + SCAN_WS_NB), 0, s>>>(
+            users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, r.t_lo, r.t_hi, r.n_pre, r.pstride,
+            w.bnd, w.bnd_m, insp);
+    } else {
+        constexpr int UG = (DP <= 128 && MT <= 32) ? 2 : 1;
+        // 8 waves share a 3-slot ring, 2 workgroups (4 waves / SIMD) per CU; every
+        // tile inserts, appends per half-block max >= tau.  Config 2 (round 3,
+        // screen = scan + select): 7.1 ms with 343 appended maxima per user;
+        // whole-tile appends 7.4-7.5 with 885 (the select reads 2.6x more);
+        // 4-wave workgroups 7.9-8.2, 4 / 6 / 8 ring slots 7.3-7.4, alternating
+        // inserts 8.1 (the lagging cut doubles the appends)
+        // ring slots capped by the CU's 160 KB of LDS (dim 128's 32-KB tiles: 4 -> 3 at UG = 1)
+        constexpr int TILE_B = scan_tb(DP) * 64 * DP, NSL_CAP = 163840 / TILE_B;
+        constexpr int NW = (UG == 2) ? 8 : 4, NSL0 = (UG == 2) ? (DP == 128 ? SCAN128_NSL : 3) : 4,
+                      NSL = NSL0 < NSL_CAP ? NSL0 : NSL_CAP;
+        static_assert(NSL >= 2, "ring");
+        launch_scan_v<DP, NW, NSL, UG, MT>(users, n_users, cat, n_items, dim, k, w, s);
     }
-    // 8 waves share a 3-slot ring, 2 workgroups (4 waves / SIMD) per CU; every
-    // tile inserts, appends per half-block max >= tau.  Config 2 (round 3,
-    // screen = scan + select): 7.1 ms with 343 appended maxima per user;
-    // whole-tile appends 7.4-7.5 with 885 (the select reads 2.6x more);
-    // 4-wave workgroups 7.9-8.2, 4 / 6 / 8 ring slots 7.3-7.4, alternating
-    // inserts 8.1 (the lagging cut doubles the appends)
-    // ring slots capped by the CU's 160 KB of LDS (dim 128's 32-KB tiles: 4 -> 3 at UG = 1)
-    constexpr int TILE_B = scan_tb(DP) * 64 * DP, NSL_CAP = 163840 / TILE_B;
-    constexpr int NW = (UG == 2) ? 8 : 4, NSL0 = (UG == 2) ? (DP == 128 ? NRK_SCAN128_NSL : 3) : 4,
-                  NSL = NSL0 < NSL_CAP ? NSL0 : NSL_CAP;
-    static_assert(NSL >= 2, "ring");
-    launch_scan_v<DP, NW, NSL, UG, MT, WPE>(users, n_users, cat, n_items, dim, k, w, s);
 }
 
 template <int DP>
@@ -3193,9 +3133,9 @@ static int ip_range(IpWs& w, int64_t n_items, int dim, int64_t blk_lo, int64_t b
     return NRK_OK;
 }
 
-// config-4 shard bounds from the scan's register lists (ip_scan_kernel's
-// epilogue) instead of a pass over the appended maxima (ip_shard_bound_kernel)
-// the scan's epilogue merges lists of up to 32 per lane (k <= 64)
+// config-4 shard bounds from the scan's register lists (the scan kernels'
+// epilogue) instead of a pass over the appended maxima (ip_shard_bound_kernel): the
+// scan's epilogue merges lists of up to 32 per lane (k <= 64)
 static inline bool shard_listbound(int k) { return (k + 1) / 2 <= 32; }
 
 // persistent grid of the shard kernels: SH_WG_PER_CU 4-wave workgroups per CU
@@ -3238,6 +3178,57 @@ static void launch_exact(const float* users, int64_t n_users, const float* items
                                               w.ovf_count + 1, out_s, out_r, out_e);
 }
 
+// The one-wave-per-user sorts (ip_bound, ip_apply_bound, topk_merge) by their
+// entry count: fn(E, ns) with E = 1, 2, 4 entries per lane in registers
+// (ns = 64 E), or E = 0 and the next power of two in dynamic LDS
+template <class F>
+static void with_sort_width(int total, F&& fn) {
+    if (total <= 64) fn(std::integral_constant<int, 1>{}, 64);
+    else if (total <= 128) fn(std::integral_constant<int, 2>{}, 128);
+    else if (total <= 256) fn(std::integral_constant<int, 4>{}, 256);
+    else fn(std::integral_constant<int, 0>{}, next_pow2(total));
+}
+template <int E>
+static size_t sort_lds_bytes(int ns) {
+    return E ? 0 : 4 * (size_t)ns * sizeof(Cand);
+}
+
+// The refine's band: the select's per-user slots in the workspace (n_src ==
+// 0), or the fixed-slot exchange of the catalog-sharded owner protocol
+struct RefineBand {
+    const uint2* cand;
+    int bandcap;
+    const int32_t* cnt;
+    const float2* ucut;
+    int n_src = 0;
+    int64_t src_users = 0;
+    int x_cap = 0;
+    const int32_t* src_cnt = nullptr;
+};
+
+// ip_refine_kernel by (DS4, SV, FK): the staged / direct dims, 256 survivors
+// for k > 64, and the u64 key sort where one lane holds one survivor (k <= 64)
+// and nobody reads the exact scores
+static void launch_refine(const float* users, int64_t n_users, const float* items, const uint8_t* cat, int64_t n_items,
+                          int dim, int k, int64_t row_offset, const RefineBand& b, const IpWs& w, float* out_s,
+                          int32_t* out_r, double* out_e, hipStream_t s) {
+    const int g2 = (int)((n_users + 3) / 4);
+    auto go = [&](auto ds4, auto sv, auto fk) {
+        ip_refine_kernel<decltype(ds4)::value, decltype(sv)::value, decltype(fk)::value><<<g2, 256, 0, s>>>(
+            users, n_users, items, cat, n_items, dim, k, row_offset, b.cand, b.bandcap, b.cnt, b.ucut, w.ovf_flag,
+            w.ovf_list, w.ovf_count, out_s, out_r, out_e, b.n_src, b.src_users, b.x_cap, b.src_cnt);
+    };
+    auto by_sv = [&](auto ds4) {
+        if (k > 64) go(ds4, std::integral_constant<int, 256>{}, std::false_type{});
+        else if (out_e) go(ds4, std::integral_constant<int, 128>{}, std::false_type{});
+        else go(ds4, std::integral_constant<int, 128>{}, std::true_type{});
+    };
+    if (dim == 32) by_sv(std::integral_constant<int, 8>{});
+    else if (dim == 16) by_sv(std::integral_constant<int, 4>{});
+    else if (dim == 64) by_sv(std::integral_constant<int, 16>{});
+    else by_sv(std::integral_constant<int, 0>{});
+}
+
 }  // namespace nrk
 
 using namespace nrk;
@@ -3245,7 +3236,7 @@ using namespace nrk;
 extern "C" {
 
 #if NRK_SCAN_STAMP
-// dev-only: the phase stamps of the last ip_scan_kernel launch (1024 x 8 u64)
+// dev-only: the phase stamps of the last scan launch (1024 x 8 u64)
 int nrk_dev_scan_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(scan_stamps), sizeof(scan_stamps)) == hipSuccess ? 0 : -1;
 }
@@ -3394,27 +3385,10 @@ int nrk_ip_topk_finish(const float* users, int64_t n_users, const float* items,
     NRK_REQUIRE(out_scores && out_rows, "null output");
     const IpWs w = ip_ws_layout(workspace, n_users, n_items, k, dim);
     hipStream_t s = as_stream(stream);
-    const int g2 = (int)((n_users + 3) / 4);
     const uint8_t* cat = reinterpret_cast<const uint8_t*>(catalog);
-#define NRK_REFINE(DS4, SV, FK)                                                                                \
-    ip_refine_kernel<DS4, SV, FK><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset, \
-                                                     w.cand, w.bandcap, w.cnt, w.ucut, w.ovf_flag, w.ovf_list, \
-                                                     w.ovf_count, out_scores, out_rows, out_exact)
-    // the u64 key sort exists where one lane holds one survivor (k <= 64)
-#define NRK_REFINE_SV(DS4)                                  \
-    do {                                                    \
-        if (k > 64) NRK_REFINE(DS4, 256, false);            \
-        else if (out_exact) NRK_REFINE(DS4, 128, false);    \
-        else NRK_REFINE(DS4, 128, true);                    \
-    } while (0)
-    if (k <= IP_KFAST || n_items == 0) {
-        if (dim == 32) NRK_REFINE_SV(8);
-        else if (dim == 16) NRK_REFINE_SV(4);
-        else if (dim == 64) NRK_REFINE_SV(16);
-        else NRK_REFINE_SV(0);
-    }
-#undef NRK_REFINE_SV
-#undef NRK_REFINE
+    if (k <= IP_KFAST || n_items == 0)
+        launch_refine(users, n_users, items, cat, n_items, dim, k, row_offset,
+                      RefineBand{w.cand, w.bandcap, w.cnt, w.ucut}, w, out_scores, out_rows, out_exact, s);
     if (n_items > 0) launch_exact(users, n_users, items, n_items, dim, k, row_offset, w, out_scores, out_rows, out_exact, s);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -3451,16 +3425,12 @@ int nrk_ip_topk_bound(const float* users, int64_t n_users, const void* catalog, 
     const CatalogHdr* hdr = reinterpret_cast<const CatalogHdr*>(
         reinterpret_cast<const uint8_t*>(catalog) + catalog_body_bytes(n_items, pad_dim(dim)));
     const int grid = (int)((n_users + 3) / 4);
-    const int need = std::max(w.bandcap, m);
-#define NRK_BOUND(E, NS)                                                                                    \
-    ip_bound_kernel<E><<<grid, 256, (E) ? 0 : 4 * (NS) * sizeof(Cand), s>>>(users, n_users, dim, hdr, w.cand, \
-                                                                           w.bandcap, w.cnt, w.ucut, m, NS,  \
-                                                                           out_bound)
-    if (need <= 64) NRK_BOUND(1, 64);
-    else if (need <= 128) NRK_BOUND(2, 128);
-    else if (need <= 256) NRK_BOUND(4, 256);
-    else NRK_BOUND(0, next_pow2(need));
-#undef NRK_BOUND
+    // the band (ip_bandcap: 96 entries at least, so never the 64-wide sort) or m
+    with_sort_width(std::max(w.bandcap, m), [&](auto ec, int ns) {
+        constexpr int E = decltype(ec)::value;
+        ip_bound_kernel<E><<<grid, 256, sort_lds_bytes<E>(ns), s>>>(users, n_users, dim, hdr, w.cand, w.bandcap, w.cnt,
+                                                                    w.ucut, m, ns, out_bound);
+    });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -3479,13 +3449,10 @@ int nrk_ip_topk_apply_bound(int64_t n_users, const float* bounds, int n_lists, i
     if (k > n_lists * m) return NRK_OK;  // fewer values than k: no bound, cut unchanged
     const int tot = n_lists * m, grid = (int)((n_users + 3) / 4);
     hipStream_t s = as_stream(stream);
-#define NRK_APPLY(E, NS) \
-    ip_apply_bound_kernel<E><<<grid, 256, (E) ? 0 : 4 * (NS) * sizeof(Cand), s>>>(w.ucut, n_users, bounds, n_lists, m, k, NS)
-    if (tot <= 64) NRK_APPLY(1, 64);
-    else if (tot <= 128) NRK_APPLY(2, 128);
-    else if (tot <= 256) NRK_APPLY(4, 256);
-    else NRK_APPLY(0, next_pow2(tot));
-#undef NRK_APPLY
+    with_sort_width(tot, [&](auto ec, int ns) {
+        constexpr int E = decltype(ec)::value;
+        ip_apply_bound_kernel<E><<<grid, 256, sort_lds_bytes<E>(ns), s>>>(w.ucut, n_users, bounds, n_lists, m, k, ns);
+    });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -3571,26 +3538,11 @@ int nrk_ip_topk_refine_x(const float* users, int64_t n_users, const float* items
     }
     ip_ovf_collect_kernel<<<(int)std::min<int64_t>((n_users + 255) / 256, 4096), 256, 0, s>>>(
         n_users, ovf_in, w.ovf_flag, w.ovf_list, w.ovf_count);
-    const int g2 = (int)((n_users + 3) / 4);
     const uint8_t* cat = reinterpret_cast<const uint8_t*>(catalog);
-    const uint2* bd = reinterpret_cast<const uint2*>(band);
-    const float2* uc = reinterpret_cast<const float2*>(ucut);
-#define NRK_REFINE(DS4, SV, FK)                                                                                      \
-    ip_refine_kernel<DS4, SV, FK><<<g2, 256, 0, s>>>(users, n_users, items, cat, n_items, dim, k, row_offset, bd, 0, \
-                                                     nullptr, uc, w.ovf_flag, w.ovf_list, w.ovf_count, out_scores,   \
-                                                     out_rows, out_exact, n_src, src_users, x_cap, src_cnt)
-#define NRK_REFINE_SV(DS4)                                  \
-    do {                                                    \
-        if (k > 64) NRK_REFINE(DS4, 256, false);            \
-        else if (out_exact) NRK_REFINE(DS4, 128, false);    \
-        else NRK_REFINE(DS4, 128, true);                    \
-    } while (0)
-    if (dim == 32) NRK_REFINE_SV(8);
-    else if (dim == 16) NRK_REFINE_SV(4);
-    else if (dim == 64) NRK_REFINE_SV(16);
-    else NRK_REFINE_SV(0);
-#undef NRK_REFINE_SV
-#undef NRK_REFINE
+    launch_refine(users, n_users, items, cat, n_items, dim, k, row_offset,
+                  RefineBand{reinterpret_cast<const uint2*>(band), 0, nullptr, reinterpret_cast<const float2*>(ucut),
+                             n_src, src_users, x_cap, src_cnt},
+                  w, out_scores, out_rows, out_exact, s);
     if (n_items > 0) launch_exact(users, n_users, items, n_items, dim, k, row_offset, w, out_scores, out_rows, out_exact, s);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -3609,15 +3561,11 @@ int nrk_topk_merge(const double* in_exact, const int32_t* in_rows, int n_lists, 
     NRK_REQUIRE(in_exact && in_rows && out_scores && out_rows, "null pointer");
     hipStream_t s = as_stream(stream);
     const int grid = (int)((n_users + 3) / 4);
-#define NRK_MERGE(E, NS)                                                                                    \
-    topk_merge_kernel<E><<<grid, 256, (E) ? 0 : 4 * (NS) * sizeof(Cand), s>>>(in_exact, in_rows, n_lists,      \
-                                                                              list_stride, n_users, k_in, k_out, \
-                                                                              NS, out_scores, out_rows, out_exact)
-    if (tot <= 64) NRK_MERGE(1, 64);
-    else if (tot <= 128) NRK_MERGE(2, 128);
-    else if (tot <= 256) NRK_MERGE(4, 256);
-    else NRK_MERGE(0, next_pow2(tot));
-#undef NRK_MERGE
+    with_sort_width(tot, [&](auto ec, int ns) {
+        constexpr int E = decltype(ec)::value;
+        topk_merge_kernel<E><<<grid, 256, sort_lds_bytes<E>(ns), s>>>(in_exact, in_rows, n_lists, list_stride, n_users,
+                                                                      k_in, k_out, ns, out_scores, out_rows, out_exact);
+    });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }

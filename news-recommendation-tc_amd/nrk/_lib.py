@@ -10,7 +10,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# NRK_LIB_PATH: developer override (e.g. the instrumented build under build_stats/)
+# NRK_LIB_PATH: developer override (e.g. a `make dev` build under build_dev/)
 LIB_PATH = os.environ.get("NRK_LIB_PATH") or os.path.join(_HERE, "libnrk.so")
 
 NRK_OK, NRK_EINVAL, NRK_EHIP, NRK_EUNSUPPORTED = 0, 1, 2, 3

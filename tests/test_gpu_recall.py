@@ -353,11 +353,18 @@ def test_ip_topk_catalog_body_near_2gib(ops):
     assert np.array_equal(s.cpu().numpy(), so)
 
 
-@pytest.mark.parametrize("n_shards", [2, 3, 8])
-def test_catalog_shards_merge_equals_single(ops, n_shards):
+@pytest.mark.parametrize("n_shards,K", [
+    pytest.param(2, 31, id="2"), pytest.param(3, 31, id="3"), pytest.param(8, 31, id="8"),
+    pytest.param(2, 64, id="2-k64"), pytest.param(2, 128, id="2-k128"), pytest.param(129, 7, id="129-k7")])
+def test_catalog_shards_merge_equals_single(ops, n_shards, K):
     """Config-4 data path on one GPU: per-shard exact top-k with global rows
     (row_offset) + nrk_topk_merge == the unsharded result, incl. a cross-shard
-    exact tie (lower global row wins)."""
+    exact tie (lower global row wins).  The sort width of nrk_ip_topk_bound
+    follows the band (96 entries at k = 31: 2 per lane; 160 at k = 64: 4 per
+    lane; 288 at k = 128: the LDS sort), that of nrk_ip_topk_apply_bound the
+    n_shards * m exchanged bounds (34-40 at k = 31: 1 per lane; 66 at 2 x 33:
+    2 per lane; 130 at 2 x 65: 4 per lane; 258 at 129 x 2, k = 7: the LDS
+    sort, with 129 x 7 = 903 entries for nrk_topk_merge's own LDS sort)."""
     from nrk.dist import HipShard, bound_width, catalog_sharded_topk, shard_range
 
     rng = np.random.default_rng(n_shards)
@@ -365,7 +372,6 @@ def test_catalog_shards_merge_equals_single(ops, n_shards):
     users[7] = 0.0  # zero user: all-tie row, lowest global rows win
     items = _unit(rng.standard_normal((5000, 32)))
     items[4990] = items[10]
-    K = 31
     so, ro = oracle.ip_topk(users, items, K)
     u = _dev(users)
     for exchange in (False, True):
@@ -513,7 +519,7 @@ def test_catalog_owner_refine_full_size(ops):
 
 @pytest.mark.parametrize("d", [16, 32, 64])
 def test_screen_eps_bounds_the_fp16_rounding(ops, d):
-    """The screen's per-user error bound (ucut.y, ip_topk.hip ip_screen_kernel:
+    """The screen's per-user error bound (ucut.y, ip_topk.hip scan_user_setup:
     ||du|| max||v|| + ||u|| max||dv|| + ||du|| max||dv|| + accumulation) must
     cover |fp16 score - exact| for every (user, item): the fp16 scores are
     re-derived here exactly (float16 rounding of the power-of-two scaled
