@@ -9,20 +9,30 @@
 // (DIN.py:39-44), so each Dice splits the forward into phases with a
 // batch-wide reduction in between.  One call scores every Dice batch of a
 // pass (segments of S samples), one launch per phase:
-//   1. din_att_h      h[b,t,:] = (Wk - Wd) k_t + (Wq + Wd) q + Wp (q .* k_t) + b0
+//   1. attention h    h[b,t,:] = (Wk - Wd) k_t + (Wq + Wd) q + Wp (q .* k_t) + b0
 //                     (= Linear(512->36) on [k, q, q-k, q.*k], DIN.py:105-114,
 //                     with the batch-invariant parts folded by nrk_din_prepare);
-//                     per-block fp64 column sums of h and h^2.
+//                     per-block fp64 column sums of h and h^2.  One of:
+//                     din_tm_plan + din_att_tm (position-major: bf16 tables,
+//                     T <= 64, <= 4 item features, h1 <= 256);
+//                     din_att_h2 (sample-major, T <= 64: fp32 tables with 1 or
+//                     2 item features, bf16 tables with <= 4 when h1 > 256);
+//                     din_att_h (every other shape: one t-tile per wave at
+//                     T <= 64, two at T > 64).
 //   2. col_stats      mean / unbiased std per (t, j) (deterministic, fixed order).
-//   3. din_wh         Dice -> Linear(36->1) -> * mask (no softmax, :117-124),
+//   3. din_wh2        Dice -> Linear(36->1) -> * mask (no softmax, :117-124),
 //                     weighted history sum wh (:276).
 //   4. din_mlp1       Linear(928->h1) on [user, ctx, cand, wh] (:279-282), the
 //                     embedding parts gathered straight from the table; 5. col_stats,
 //   6. din_mlp2       Dice-on-load -> Linear(h1->h2); 7. col_stats,
 //   8. din_head       Dice -> Linear(h2->1) -> sigmoid (:282-284).
 // The general path (T > 64 or h1 > 256) assembles the MLP input with
-// din_att_out and runs the f32 MFMA din_gemm instead of 3, 4 and 6.
+// din_att_out and runs the f32 MFMA din_gemm<false> instead of 3 and 4; the
+// second layer is din_gemm<true> instead of 6 on the general path and when
+// h2 > 128.
 #include "din_common.h"
+
+#include <atomic>
 
 namespace nrk {
 
@@ -66,27 +76,37 @@ __device__ __forceinline__ float dice(float x, float mean, float std) {
 
 constexpr int DIN_JT = 3;  // 36 columns -> 3 tiles of 16
 
+// din_att_h and din_att_h2 share the two helpers below.  Their weight
+// preload, M_b / c_b build and per-tile MFMA chain are the same text too, but
+// stay written out in both: as shared helpers each of them moved the
+// kernels' instruction streams and register counts.
 
-template <typename TT>
-__device__ __forceinline__ void load8(const TT* p, float (&v)[8]);
-template <>
-__device__ __forceinline__ void load8<float>(const float* p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0];
-    const float4 b = reinterpret_cast<const float4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void load8<uint16_t>(const uint16_t* p, float (&v)[8]) {
-    const uint4 a = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+// 8 consecutive table elements from their raw bits (fp32: two 16-B pieces,
+// bf16: one, two elements per word)
+template <int RW>
+__device__ __forceinline__ void unpack8(const din_u4 (&raw)[RW], float (&v)[8]) {
+    if constexpr (RW == 2) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+        for (int e = 0; e < 4; ++e) {
+            v[e] = __uint_as_float(raw[0][e]);
+            v[4 + e] = __uint_as_float(raw[1][e]);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = __uint_as_float(raw[0][i] << 16);
+            v[2 * i + 1] = __uint_as_float(raw[0][i] & 0xFFFF0000u);
+        }
     }
 }
 
+// a k row piece -> A fragments (hi / lo at scale s_k)
+template <int RW>
+__device__ __forceinline__ void att_afrag(const din_u4 (&raw)[RW], float s_k, din_half8& hi, din_half8& lo) {
+    float v[8];
+    unpack8(raw, v);
+    split8(v, s_k, hi, lo);
+}
 
 // Segments: the N samples are scored as consecutive Dice batches of S
 // (DINRanker.predict's DataLoader batches, DIN.py:1245-1283); workgroup
@@ -202,23 +222,7 @@ __global__ __launch_bounds__(256) void din_att_h_kernel(
 #pragma unroll
         for (int a = 0; a < NTW; ++a)
 #pragma unroll
-            for (int s = 0; s < NI; ++s) {
-                float v[8];
-                if (F32) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = __uint_as_float(raw[a][s][0][e]);
-                        v[4 + e] = __uint_as_float(raw[a][s][RW - 1][e]);
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        v[2 * i] = __uint_as_float(raw[a][s][0][i] << 16);
-                        v[2 * i + 1] = __uint_as_float(raw[a][s][0][i] & 0xFFFF0000u);
-                    }
-                }
-                split8(v, sc.s_k, ahi[a][s], alo[a][s]);
-            }
+            for (int s = 0; s < NI; ++s) att_afrag(raw[a][s], sc.s_k, ahi[a][s], alo[a][s]);
         // (2) query embedding
         if (tid < ID) qs[tid] = q_of(qv);
 #pragma unroll
@@ -418,23 +422,7 @@ __global__ __launch_bounds__(256, 2) void din_att_h2_kernel(
         // (1) this wave's k rows -> A fragments; q -> LDS
         din_half8 ahi[NI], alo[NI];
 #pragma unroll
-        for (int s = 0; s < NI; ++s) {
-            float v[8];
-            if (F32) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = __uint_as_float(raw[s][0][e]);
-                    v[4 + e] = __uint_as_float(raw[s][RW - 1][e]);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    v[2 * i] = __uint_as_float(raw[s][0][i] << 16);
-                    v[2 * i + 1] = __uint_as_float(raw[s][0][i] & 0xFFFF0000u);
-                }
-            }
-            split8(v, sc.s_k, ahi[s], alo[s]);
-        }
+        for (int s = 0; s < NI; ++s) att_afrag(raw[s], sc.s_k, ahi[s], alo[s]);
         if (tid < ID) qs[tid] = F32 ? __uint_as_float(qv) : __uint_as_float(qv << 16);
         // (2) prefetch: indices of b + 3G, then rows / q of b + 2G into the
         // registers just consumed
@@ -595,8 +583,8 @@ __global__ void din_scales_kernel(const float* __restrict__ prep_ap, int ID, con
 //   are left unwritten: their mask is 0, and din_wh2 never reads a masked
 //   row's h.  At config 3 (hist_len ~ U[1, 50], 20% empty) that is ~21 of
 //   50 rows per sample.
-// * Position-major tiles: a workgroup (4 waves, one per SIMD, each holding
-//   all weight fragments in registers; ~100 KB of LDS)
+// * Position-major tiles: a workgroup (8 waves, two per SIMD, the weight
+//   fragments in LDS; ~150 KB of LDS)
 //   takes a run of SW = 128 samples of ONE Dice batch, sorts them by n_b
 //   (descending, stable), so the samples with a real row at position t are
 //   the prefix [0, c_t) -- ceil(c_t / 16) tiles whose rows all share t.  A
@@ -608,27 +596,15 @@ __global__ void din_scales_kernel(const float* __restrict__ prep_ap, int ID, con
 // * Per tile the k rows of the next two tiles and the indices of the third
 //   are in flight (issued before the tile's MFMAs); all loads are unconditional (clamped rows), h goes out through
 //   buffer stores whose out-of-range offsets the hardware drops.
-// dev-only A/B switch (make devdin DEVFLAGS=-DNRK_TM_DEV=n; the product
-// build leaves it 0): 1 skips phase 7, 2 its stores, 3 its MFMAs, 4 phases 4-6
-#ifndef NRK_TM_DEV
-#define NRK_TM_DEV 0
-#endif
+// Settled by measurement (commit 6771b0c is the last with the build switches
+// NRK_TM_NW, NRK_TM_WRING and NRK_TM_DEV): four waves, one per SIMD, with the
+// weight fragments in registers were issue-bound at ~2.5k cycles per tile
+// against ~1.7k for eight; W double-buffered per k-step (24 fragments live)
+// spilled 45 VGPRs at NI = 4, the 3-slot ring below runs in 254 with no
+// scratch.
 constexpr int TM_SW = 128;  // samples per workgroup
-// waves per workgroup: 8 (two per SIMD, the weight fragments in LDS, read
-// one k-step ahead) or, dev builds only, 4 (one per SIMD, the fragments in
-// registers -- issue-bound: ~2.5k cycles per tile against ~1.5k)
-#ifndef NRK_TM_NW
-#define NRK_TM_NW 8
-#endif
-constexpr int TM_NW = NRK_TM_NW;
-constexpr bool TM_WLDS = TM_NW == 8;
-// W fragments from LDS in a 3-slot ring per (k-step, column tile) group (1)
-// or double-buffered per k-step (0, round 4)
-#ifndef NRK_TM_WRING
-#define NRK_TM_WRING 1
-#endif
-constexpr bool TM_WRING = NRK_TM_WRING;
-constexpr int TM_NT = TM_NW * 64;
+constexpr int TM_NW = 8;    // waves per workgroup: two per SIMD, the weight fragments in LDS
+constexpr int TM_NT = 512;  // threads per workgroup (TM_NW waves)
 constexpr int TM_TMAX = 64; // positions (T)
 
 struct DinScalesTM {
@@ -731,7 +707,7 @@ typedef uint32_t tm_u4 __attribute__((ext_vector_type(4)));
 
 static inline size_t din_tm_lds(int NI, int T) {
     const int ID = NI * DIN_E;
-    return (TM_WLDS ? (size_t)3 * NI * 4 * 1024 : 0)   // W fragments
+    return (size_t)3 * NI * 4 * 1024                   // W fragments
            + (size_t)TM_SW * (ID * 2 + 16)             // q rows (fp16, padded stride)
            + (size_t)DIN_H * (TM_SW + 4) * 4           // c^T (acc init), padded stride
            + (size_t)TM_SW * DIN_H * 4                 // pad-row h
@@ -757,6 +733,8 @@ constexpr int TM_PLAN = TM_SW + TM_TMAX;
 
 // dev-only phase stamps (make devdin DEVFLAGS=-DNRK_TM_STAMP=1, read by
 // nrk_dev_tm_stamps): per workgroup, shader cycles spent in each phase
+// (TM_STAMP, since the previous phase stamp) and in each part of a main-loop
+// step (TM_SSTAMP, since the step's previous stamp)
 #ifndef NRK_TM_STAMP
 #define NRK_TM_STAMP 0
 #endif
@@ -768,9 +746,18 @@ __device__ unsigned long long tm_stamps[1024 * 12];
         stp[k] += t_now_ - t_prev;                            \
         t_prev = t_now_;                                      \
     } while (0)
+#define TM_SSTAMP(k)                                          \
+    do {                                                      \
+        const uint64_t t_now_ = __builtin_readcyclecounter(); \
+        stp[k] += t_now_ - t_s;                               \
+        t_s = t_now_;                                         \
+    } while (0)
 #else
 #define TM_STAMP(k) \
     do {            \
+    } while (0)
+#define TM_SSTAMP(k) \
+    do {             \
     } while (0)
 #endif
 
@@ -848,7 +835,7 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
     constexpr int CTS = TM_SW + 4;   // c^T row stride (floats)
     extern __shared__ __attribute__((aligned(16))) uint8_t tm_lds[];
     din_half8* wl = reinterpret_cast<din_half8*>(tm_lds);
-    uint8_t* ql = tm_lds + (TM_WLDS ? 3 * NI * 4 * 1024 : 0);
+    uint8_t* ql = tm_lds + 3 * NI * 4 * 1024;
     float* ct = reinterpret_cast<float*>(ql + TM_SW * QS);
     float* hp = ct + DIN_H * CTS;
     double2* R = reinterpret_cast<double2*>(hp + TM_SW * DIN_H);
@@ -862,21 +849,12 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
     const DinScalesTM sc = *reinterpret_cast<const DinScalesTM*>(tm);
     const din_half8* wpack = reinterpret_cast<const din_half8*>(tm + 256);
     const din_half8* qdpack = wpack + 3 * NI * 4 * 64;
-    // W fragments (12 NI per lane: the B operand of every tile), once per
-    // workgroup: to LDS (TM_WLDS; published by the first run's barrier) or
-    // to registers
-    din_half8 wr[TM_WLDS ? 1 : 3][TM_WLDS ? 1 : NI][4];
-    if constexpr (TM_WLDS) {
+    // W fragments (12 NI per lane: the B operand of every tile) to LDS, once
+    // per workgroup (published by the first run's barrier)
+    {
         const tm_u4* src = reinterpret_cast<const tm_u4*>(wpack);
         tm_u4* d = reinterpret_cast<tm_u4*>(wl);
         for (int c = tid; c < 3 * NI * 4 * 64; c += TM_NT) d[c] = src[c];
-    } else {
-#pragma unroll
-        for (int jt = 0; jt < 3; ++jt)
-#pragma unroll
-            for (int s = 0; s < NI; ++s)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) wr[jt][s][c] = wpack[((jt * NI + s) * 4 + c) * 64 + lane];
     }
     const int64_t n_blk = (N + S - 1) / S * G;
 #if NRK_TM_STAMP
@@ -976,80 +954,33 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
             const int j = 16 * jt + lr < DIN_H ? 16 * jt + lr : DIN_H - 1;
             acc[jt] = *reinterpret_cast<const din_f4*>(ct + j * CTS + 16 * i + 4 * lg);
         }
-        if constexpr (TM_WLDS && TM_WRING) {
-            // the (k-step s, column tile jt) groups' 4 fragments each, read two
-            // groups (10 MFMAs) ahead in a 3-slot ring: 12 fragments live
-            // instead of a whole k-step double-buffered (24: the NI = 4
-            // instantiation spilled 45 VGPRs at 256)
-            din_half8 wq[3][4];
-            auto wread = [&](int q, din_half8 (&w)[4]) {
-                const int s = q / 3, jt = q % 3;
+        // the (k-step s, column tile jt) groups' 4 fragments each, read two
+        // groups (10 MFMAs) ahead in a 3-slot ring: 12 fragments live
+        din_half8 wq[3][4];
+        auto wread = [&](int q, din_half8 (&w)[4]) {
+            const int s = q / 3, jt = q % 3;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) w[c] = wl[((jt * NI + s) * 4 + c) * 64 + lane];
-            };
-            wread(0, wq[0]);
-            wread(1, wq[1]);
-            din_half8 ph, pl;
-            static_for<3 * NI>([&](auto qc) {
-                constexpr int q = decltype(qc)::value, s = q / 3, jt = q % 3;
-                if constexpr (q + 2 < 3 * NI) wread(q + 2, wq[(q + 2) % 3]);
-                if constexpr (jt == 0) {
-                    const din_half8 qf = *reinterpret_cast<const din_half8*>(ql + pa * QS + (DIN_E * s + 8 * lg) * 2);
-                    __builtin_amdgcn_sched_barrier(0);
-                    ph = kf[s] * qf;
-                    pl = __builtin_elementwise_fma(kf[s], qf, -ph);
-                }
-                const din_half8(&w)[4] = wq[q % 3];
-                acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[0], acc[jt], 0, 0, 0);
-                acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[1], acc[jt], 0, 0, 0);
-                acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[2], acc[jt], 0, 0, 0);
-                acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[3], acc[jt], 0, 0, 0);
-                acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, w[2], acc[jt], 0, 0, 0);
-            });
-        } else if constexpr (TM_WLDS) {
-            // k-step s + 1's 12 fragments are read while k-step s's 15 MFMAs
-            // run (two register sets; the barrier keeps the reads ahead)
-            din_half8 wb[2][3][4];
-            auto wread = [&](int s, din_half8 (&w)[3][4]) {
-#pragma unroll
-                for (int jt = 0; jt < 3; ++jt)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) w[jt][c] = wl[((jt * NI + s) * 4 + c) * 64 + lane];
-            };
-            wread(0, wb[0]);
-#pragma unroll
-            for (int s = 0; s < NI; ++s) {
-                if (s + 1 < NI) wread(s + 1, wb[(s + 1) & 1]);
+            for (int c = 0; c < 4; ++c) w[c] = wl[((jt * NI + s) * 4 + c) * 64 + lane];
+        };
+        wread(0, wq[0]);
+        wread(1, wq[1]);
+        din_half8 ph, pl;
+        static_for<3 * NI>([&](auto qc) {
+            constexpr int q = decltype(qc)::value, s = q / 3, jt = q % 3;
+            if constexpr (q + 2 < 3 * NI) wread(q + 2, wq[(q + 2) % 3]);
+            if constexpr (jt == 0) {
                 const din_half8 qf = *reinterpret_cast<const din_half8*>(ql + pa * QS + (DIN_E * s + 8 * lg) * 2);
                 __builtin_amdgcn_sched_barrier(0);
-                const din_half8 ph = kf[s] * qf;
-                const din_half8 pl = __builtin_elementwise_fma(kf[s], qf, -ph);
-                const din_half8(&w)[3][4] = wb[s & 1];
-#pragma unroll
-                for (int jt = 0; jt < 3; ++jt) {
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[jt][0], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[jt][1], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[jt][2], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[jt][3], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, w[jt][2], acc[jt], 0, 0, 0);
-                }
+                ph = kf[s] * qf;
+                pl = __builtin_elementwise_fma(kf[s], qf, -ph);
             }
-        } else {
-#pragma unroll
-            for (int s = 0; s < NI; ++s) {
-                const din_half8 qf = *reinterpret_cast<const din_half8*>(ql + pa * QS + (DIN_E * s + 8 * lg) * 2);
-                const din_half8 ph = kf[s] * qf;
-                const din_half8 pl = __builtin_elementwise_fma(kf[s], qf, -ph);
-#pragma unroll
-                for (int jt = 0; jt < 3; ++jt) {
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], wr[jt][s][0], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], wr[jt][s][1], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, wr[jt][s][2], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, wr[jt][s][3], acc[jt], 0, 0, 0);
-                    acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, wr[jt][s][2], acc[jt], 0, 0, 0);
-                }
-            }
-        }
+            const din_half8(&w)[4] = wq[q % 3];
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[0], acc[jt], 0, 0, 0);
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s], w[1], acc[jt], 0, 0, 0);
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[2], acc[jt], 0, 0, 0);
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, w[3], acc[jt], 0, 0, 0);
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, w[2], acc[jt], 0, 0, 0);
+        });
     };
 
     TM_STAMP(2);
@@ -1060,7 +991,7 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
 #pragma unroll
         for (int s = 0; s < NI; ++s) k0[s] = tab16[row_base[n_user + s] * 4 + lg];
         const int pad_lo = cnt[T - 1];
-        for (int i = pad_lo / 16 + wv; NRK_TM_DEV != 4 && i * 16 < nw; i += TM_NW) {
+        for (int i = pad_lo / 16 + wv; i * 16 < nw; i += TM_NW) {
             const int pa = 16 * i + lr < nw ? 16 * i + lr : nw - 1;
             din_f4 acc[3];
             tile_mfma(i, k0, pa, acc);
@@ -1081,7 +1012,7 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
     // (sorted positions [c_t, c_{t-1}), c_{-1} = nw), into R
     for (int e = tid; e < T * DIN_H; e += TM_NT) {
         const int t = e / DIN_H, j = e % DIN_H;
-        const int lo = cnt[t], hi = NRK_TM_DEV == 4 ? lo : t == 0 ? nw : cnt[t - 1];
+        const int lo = cnt[t], hi = t == 0 ? nw : cnt[t - 1];
         double s = 0.0, ss = 0.0;
         for (int p = lo; p < hi; ++p) {
             const double v = (double)hp[p * DIN_H + j];
@@ -1184,16 +1115,6 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
     auto step = [&](din_half8 (&kcur)[NI], int4& ixcur, din_half8 (&kfar)[NI], const int4& ixfar) {
 #if NRK_TM_STAMP
         uint64_t t_s = __builtin_readcyclecounter();
-#define TM_SSTAMP(k)                                          \
-    do {                                                      \
-        const uint64_t t_now_ = __builtin_readcyclecounter(); \
-        stp[k] += t_now_ - t_s;                               \
-        t_s = t_now_;                                         \
-    } while (0)
-#else
-#define TM_SSTAMP(k) \
-    do {             \
-    } while (0)
 #endif
         const Job j3 = succ(j2);
         TM_SSTAMP(8);
@@ -1204,13 +1125,7 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
         // them past the chain, leaving a load latency exposed per tile)
         __builtin_amdgcn_sched_barrier(0);
         din_f4 acc[3];
-        if constexpr (NRK_TM_DEV == 3) {
-#pragma unroll
-            for (int jt = 0; jt < 3; ++jt)
-                acc[jt] = din_f4{kcur[0][0] + kcur[NI - 1][1], 0.0f, 0.0f, 0.0f} * (float)ixfar.x;
-        } else {
-            tile_mfma(j0.i, kcur, apos(j0), acc);
-        }
+        tile_mfma(j0.i, kcur, apos(j0), acc);
 #if NRK_TM_STAMP
         asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]));
 #endif
@@ -1288,7 +1203,7 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
         j1 = j2;
         j2 = j3;
     };
-    while (NRK_TM_DEV != 1 && j0.t < t_eff) {
+    while (j0.t < t_eff) {
         step(k_a, ix_a, k_c, ix_c);
         if (j0.t >= t_eff) break;
         step(k_b, ix_b, k_a, ix_a);
@@ -2242,6 +2157,44 @@ static DinWs din_ws_layout(void* base, int64_t N, int64_t S, int T, int n_user, 
     return w;
 }
 
+// -------------------------------------------------------------- dispatch --
+// Run-time shape -> template arguments.  fn(integral_constant<int, R>) for
+// the first rung R of the ascending list with v <= R (the last one when v is
+// past them all): the item-feature count {1, 2, 4, 8}, din_mlp1_nt
+// {4, 8, 13, 16}, din_mlp2_nt {2, 4, 5, 8}, din_wh2's chunk count {4, 8, 9}.
+template <int R, int... Rest, typename F>
+static void with_rung(int v, F&& fn) {
+    if constexpr (sizeof...(Rest) == 0) fn(std::integral_constant<int, R>{});
+    else if (v <= R) fn(std::integral_constant<int, R>{});
+    else with_rung<Rest...>(v, fn);
+}
+// fn(TT{}) for the table's element type: 0 = fp32, 1 = bf16 bits
+template <typename F>
+static void with_table_type(int table_dtype, F&& fn) {
+    if (table_dtype == 0) fn(float{});
+    else fn(uint16_t{});
+}
+
+// the kernels are instantiated for 1, 2, 4 and 8 (32-wide) item features
+// (ops.DinParams pads other counts); fn = the calling entry point's name
+static int din_check_n_item(const char* fn, int n_item) {
+    if (n_item == 8 || n_item == 4 || n_item == 2 || n_item == 1) return NRK_OK;
+    set_error(std::string(fn) + ": n_item must be 1, 2, 4 or 8");
+    return NRK_EUNSUPPORTED;
+}
+
+// Raise a kernel's dynamic-LDS limit to the most its instantiation can ask
+// for, once per device: `done` is the launch site's function-local static,
+// one per instantiation (as launch_exact in ip_topk.hip)
+static void lds_limit_once(std::atomic<uint64_t>& done, const void* kernel, size_t bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t dbit = 1ull << (dev & 63);
+    if (dev < 64 && (done.load(std::memory_order_acquire) & dbit)) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done.fetch_or(dbit, std::memory_order_release);
+}
+
 }  // namespace nrk
 
 using namespace nrk;
@@ -2279,8 +2232,7 @@ int nrk_din_prepare(const float* att_w0, int n_item, const void* table, int tabl
     clear_error();
     NRK_REQUIRE(att_w0 && prep && table, "null pointer");
     NRK_REQUIRE(n_item >= 1 && n_item <= 8, "n_item must be in [1, 8]");
-    // instantiated for 1, 2, 4 and 8 (32-wide) item features (ops.DinParams pads other counts)
-    if (n_item != 8 && n_item != 4 && n_item != 2 && n_item != 1) NRK_UNSUPPORTED("n_item must be 1, 2, 4 or 8");
+    if (const int e = din_check_n_item(__func__, n_item)) return e;
     NRK_REQUIRE(table_dtype == 0 || table_dtype == 1, "table_dtype must be 0 (f32) or 1 (bf16)");
     NRK_REQUIRE(n_table_rows >= 1, "n_table_rows must be >= 1");
     const int ID = n_item * DIN_E;
@@ -2344,8 +2296,7 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
         NRK_REQUIRE(S % 64 == 0, "seg_len must be a multiple of 64 when the samples span several segments");
     NRK_REQUIRE(seq_len >= 1 && seq_len <= 128, "seq_len must be in [1, 128]");
     NRK_REQUIRE(n_user >= 1 && n_ctx >= 0 && n_item >= 1, "bad feature counts");
-    // instantiated for 1, 2, 4 and 8 (32-wide) item features (ops.DinParams pads other counts)
-    if (n_item != 8 && n_item != 4 && n_item != 2 && n_item != 1) NRK_UNSUPPORTED("n_item must be 1, 2, 4 or 8");
+    if (const int e = din_check_n_item(__func__, n_item)) return e;
     NRK_REQUIRE(h1 >= 1 && h1 <= 1024 && h2 >= 1 && h2 <= 1024, "hidden sizes out of range");
     NRK_REQUIRE(table && row_base && user_idx && item_idx && hist_idx && mask && prep && att_b0 &&
                     att_w1 && att_b1 && mlp_w0 && mlp_b0 && mlp_w1 && mlp_b1 && mlp_w2 && mlp_b2 &&
@@ -2366,58 +2317,48 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
     // the fast MLP path): plan, then h + its statistics
     const bool tm_path = table_dtype == 1 && T <= TM_TMAX && n_item <= 4 && din_fast(T, h1);
     const int G_tm = (int)((S + TM_SW - 1) / TM_SW);
-    // persistent: one workgroup per CU (register- and LDS-bound)
-    static const int n_cu = [] {
-        int dev = 0, cu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-        return cu > 0 ? cu : 256;
-    }();
-    const unsigned tm_grid = (unsigned)std::min<int64_t>(n_seg * G_tm, n_cu);
-    const uint8_t* tm = reinterpret_cast<const uint8_t*>(prep) + din_tm_base(n_item);
-#define NRK_ATT_TM(NI)                                                                                 \
-    do {                                                                                               \
-        const size_t lds = din_tm_lds(NI, T);                                                          \
-        (void)hipFuncSetAttribute((const void*)din_att_tm_kernel<NI>,                                  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-        din_att_tm_kernel<NI><<<tm_grid, TM_NT, lds, s>>>(                                             \
-            reinterpret_cast<const din_half8*>(reinterpret_cast<const uint8_t*>(prep) +                \
-                                               din_tm_tab16_off(n_item)),                               \
-            row_base, n_user, item_idx, hist_idx, w.plan, batch, S, G_tm, T, tm, att_b0, w.h, w.hpart); \
-    } while (0)
-#define NRK_ATT_H(TT, NI)                                                                              \
-    do {                                                                                               \
-        if (T <= 64 && NI <= 4 && (sizeof(TT) == 2 || NI < 4))                                         \
-            din_att_h2_kernel<TT, NI><<<(unsigned)nb_att, 256, 0, s>>>(                                \
-                reinterpret_cast<const TT*>(table), row_base, n_user, item_idx, hist_idx, batch, S, G,    \
-                T, pf, att_b0, w.h, w.hpart);                                                       \
-        else if (T <= 64)                                                                              \
-            din_att_h_kernel<TT, NI, 1><<<(unsigned)nb_att, 256, 0, s>>>(                              \
-                reinterpret_cast<const TT*>(table), row_base, n_user, item_idx, hist_idx, batch, S, G,    \
-                T, pf, att_b0, w.h, w.hpart);                                                       \
-        else                                                                                           \
-            din_att_h_kernel<TT, NI, 2><<<(unsigned)nb_att, 256, 0, s>>>(                              \
-                reinterpret_cast<const TT*>(table), row_base, n_user, item_idx, hist_idx, batch, S, G,    \
-                T, pf, att_b0, w.h, w.hpart);                                                       \
-    } while (0)
     if (tm_path) {
-#define NRK_TM_PLAN(NI) din_tm_plan_kernel<NI><<<(unsigned)(n_seg * G_tm), 256, 0, s>>>(hist_idx, mask, batch, S, G_tm, T, w.plan)
-        if (n_item == 4) NRK_TM_PLAN(4); else if (n_item == 2) NRK_TM_PLAN(2); else NRK_TM_PLAN(1);
-#undef NRK_TM_PLAN
-        if (n_item == 4) NRK_ATT_TM(4); else if (n_item == 2) NRK_ATT_TM(2); else NRK_ATT_TM(1);
-    } else if (table_dtype == 0) {
-        if (n_item == 8) NRK_ATT_H(float, 8); else if (n_item == 4) NRK_ATT_H(float, 4);
-        else if (n_item == 2) NRK_ATT_H(float, 2); else NRK_ATT_H(float, 1);
+        // persistent: one workgroup per CU (register- and LDS-bound)
+        static const int n_cu = [] {
+            int dev = 0, cu = 256;
+            if (hipGetDevice(&dev) == hipSuccess)
+                (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
+            return cu > 0 ? cu : 256;
+        }();
+        const unsigned tm_grid = (unsigned)std::min<int64_t>(n_seg * G_tm, n_cu);
+        const uint8_t* pb = reinterpret_cast<const uint8_t*>(prep);
+        with_rung<1, 2, 4>(n_item, [&](auto ni) {
+            constexpr int NI = decltype(ni)::value;
+            din_tm_plan_kernel<NI><<<(unsigned)(n_seg * G_tm), 256, 0, s>>>(hist_idx, mask, batch, S, G_tm, T, w.plan);
+            static std::atomic<uint64_t> lds_set{0};
+            lds_limit_once(lds_set, (const void*)din_att_tm_kernel<NI>, din_tm_lds(NI, TM_TMAX));
+            din_att_tm_kernel<NI><<<tm_grid, TM_NT, din_tm_lds(NI, T), s>>>(
+                reinterpret_cast<const din_half8*>(pb + din_tm_tab16_off(NI)), row_base, n_user, item_idx, hist_idx,
+                w.plan, batch, S, G_tm, T, pb + din_tm_base(NI), att_b0, w.h, w.hpart);
+        });
     } else {
-        if (n_item == 8) NRK_ATT_H(uint16_t, 8); else if (n_item == 4) NRK_ATT_H(uint16_t, 4);
-        else if (n_item == 2) NRK_ATT_H(uint16_t, 2); else NRK_ATT_H(uint16_t, 1);
+        with_table_type(table_dtype, [&](auto tt) {
+            using TT = decltype(tt);
+            with_rung<1, 2, 4, 8>(n_item, [&](auto ni) {
+                constexpr int NI = decltype(ni)::value;
+                auto launch = [&](auto* kernel) {
+                    kernel<<<(unsigned)nb_att, 256, 0, s>>>(reinterpret_cast<const TT*>(table), row_base, n_user,
+                                                            item_idx, hist_idx, batch, S, G, T, pf, att_b0, w.h,
+                                                            w.hpart);
+                };
+                // T <= 64: din_att_h2 where it fits the registers (fp32 tables
+                // with 4 item features, and 8 item features, would spill)
+                if (T > 64) launch(din_att_h_kernel<TT, NI, 2>);
+                else if constexpr (NI <= 4 && (sizeof(TT) == 2 || NI < 4)) launch(din_att_h2_kernel<TT, NI>);
+                else launch(din_att_h_kernel<TT, NI, 1>);
+            });
+        });
     }
-#undef NRK_ATT_H
     const int ncol_att = T * DIN_H;
     const unsigned gs = (unsigned)n_seg;
     const int bps_att = tm_path ? G_tm : G;
     col_stats_kernel<<<dim3(gs, (ncol_att + 3) / 4), 256, 0, s>>>(w.hpart, bps_att, (int)(n_seg * bps_att),
                                                                    ncol_att, batch, S, w.hstats, w.hinv);
-#undef NRK_ATT_TM
     const int64_t nb_m = (batch + 63) / 64;
     const int bps = n_seg == 1 ? (int)nb_m : (int)(S / 64);  // 64-row GEMM blocks per segment
     if (din_fast(T, h1)) {
@@ -2432,57 +2373,42 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
         const int NT = din_mlp1_nt(h1);
         const int64_t npk = (int64_t)(IN / DIN_E) * NT * 64;
         const int gp = (int)std::min<int64_t>((npk + 255) / 256, 2048);
-#define NRK_PACK(NTV) din_w1_pack_kernel<NTV><<<gp, 256, 0, s>>>(mlp_w0, h1, IN, w1max, w.w1pack)
-        if (NT == 4) NRK_PACK(4); else if (NT == 8) NRK_PACK(8); else if (NT == 13) NRK_PACK(13); else NRK_PACK(16);
-#undef NRK_PACK
+        with_rung<4, 8, 13, 16>(NT, [&](auto nt) {
+            din_w1_pack_kernel<decltype(nt)::value><<<gp, 256, 0, s>>>(mlp_w0, h1, IN, w1max, w.w1pack);
+        });
         // din_wh2: one wave per sample; workgroups per Dice batch, about 8,192 in all
         const int nch = (T * (DIN_H / 4) + 63) / 64;
         const int gw_seg = (int)std::max<int64_t>(1, std::min<int64_t>(S, (8192 + n_seg - 1) / n_seg));
         const unsigned gw2 = (unsigned)(n_seg * gw_seg);
-#define NRK_WH2_K(TT, NI, NCH)                                                                               \
-    din_wh2_kernel<TT, NI, NCH><<<gw2, 256, din_wh2_lds(T, NI), s>>>(                                        \
-        reinterpret_cast<const TT*>(table), row_base, n_user, hist_idx, mask, batch, S, T, gw_seg, w.h, w.hinv, \
-        att_w1, att_b1, w.wh, w.whmax)
-#define NRK_WH(TT, NI)                                                                                  \
-    do {                                                                                                \
-        if (nch <= 4) NRK_WH2_K(TT, NI, 4); else if (nch <= 8) NRK_WH2_K(TT, NI, 8); else NRK_WH2_K(TT, NI, 9); \
-    } while (0)
-        if (table_dtype == 0) {
-            if (n_item == 8) NRK_WH(float, 8); else if (n_item == 4) NRK_WH(float, 4);
-            else if (n_item == 2) NRK_WH(float, 2); else NRK_WH(float, 1);
-        } else {
-            if (n_item == 8) NRK_WH(uint16_t, 8); else if (n_item == 4) NRK_WH(uint16_t, 4);
-            else if (n_item == 2) NRK_WH(uint16_t, 2); else NRK_WH(uint16_t, 1);
-        }
-#undef NRK_WH
-#undef NRK_WH2_K
         const unsigned gm = (unsigned)((batch + MLP1_ROWS - 1) / MLP1_ROWS);
-#define NRK_MLP1(TT, NTV)                                                                                 \
-    din_mlp1_kernel<TT, NTV><<<gm, 256, 0, s>>>(reinterpret_cast<const TT*>(table), row_base, n_user,     \
-                                                n_item, n_ctx, user_idx, item_idx, ctx_idx, w.wh, w.whmax, \
-                                                pf, w1max,                                                 \
-                                                reinterpret_cast<const din_u4*>(w.w1pack), mlp_b0, batch,   \
-                                                S, h1, w.z1, w.z1part, w.whmax + n_seg + 1)
-        if (table_dtype == 0) {
-            if (NT == 4) NRK_MLP1(float, 4); else if (NT == 8) NRK_MLP1(float, 8);
-            else if (NT == 13) NRK_MLP1(float, 13); else NRK_MLP1(float, 16);
-        } else {
-            if (NT == 4) NRK_MLP1(uint16_t, 4); else if (NT == 8) NRK_MLP1(uint16_t, 8);
-            else if (NT == 13) NRK_MLP1(uint16_t, 13); else NRK_MLP1(uint16_t, 16);
-        }
-#undef NRK_MLP1
+        with_table_type(table_dtype, [&](auto tt) {
+            using TT = decltype(tt);
+            const TT* tab = reinterpret_cast<const TT*>(table);
+            with_rung<1, 2, 4, 8>(n_item, [&](auto ni) {
+                with_rung<4, 8, 9>(nch, [&](auto nc) {
+                    constexpr int NI = decltype(ni)::value, NCH = decltype(nc)::value;
+                    din_wh2_kernel<TT, NI, NCH><<<gw2, 256, din_wh2_lds(T, NI), s>>>(
+                        tab, row_base, n_user, hist_idx, mask, batch, S, T, gw_seg, w.h, w.hinv, att_w1, att_b1,
+                        w.wh, w.whmax);
+                });
+            });
+            with_rung<4, 8, 13, 16>(NT, [&](auto nt) {
+                din_mlp1_kernel<TT, decltype(nt)::value><<<gm, 256, 0, s>>>(
+                    tab, row_base, n_user, n_item, n_ctx, user_idx, item_idx, ctx_idx, w.wh, w.whmax, pf, w1max,
+                    reinterpret_cast<const din_u4*>(w.w1pack), mlp_b0, batch, S, h1, w.z1, w.z1part,
+                    w.whmax + n_seg + 1);
+            });
+        });
     } else {
-    const int go = (int)(batch < 8192 ? batch : 8192);
-    if (table_dtype == 0)
-        din_att_out_kernel<float><<<go, 256, 0, s>>>(
-            reinterpret_cast<const float*>(table), row_base, n_user, n_item, n_ctx, user_idx,
-            item_idx, hist_idx, ctx_idx, mask, batch, S, T, w.h, w.hstats, att_w1, att_b1, w.mlp_in);
-    else
-        din_att_out_kernel<uint16_t><<<go, 256, 0, s>>>(
-            reinterpret_cast<const uint16_t*>(table), row_base, n_user, n_item, n_ctx, user_idx,
-            item_idx, hist_idx, ctx_idx, mask, batch, S, T, w.h, w.hstats, att_w1, att_b1, w.mlp_in);
-    din_gemm_kernel<false><<<dim3((unsigned)nb_m, (h1 + 63) / 64), 512, 0, s>>>(
-        w.mlp_in, nullptr, mlp_w0, mlp_b0, batch, S, h1, IN, w.z1, w.z1part);
+        const int go = (int)(batch < 8192 ? batch : 8192);
+        with_table_type(table_dtype, [&](auto tt) {
+            using TT = decltype(tt);
+            din_att_out_kernel<TT><<<go, 256, 0, s>>>(reinterpret_cast<const TT*>(table), row_base, n_user, n_item,
+                                                      n_ctx, user_idx, item_idx, hist_idx, ctx_idx, mask, batch, S,
+                                                      T, w.h, w.hstats, att_w1, att_b1, w.mlp_in);
+        });
+        din_gemm_kernel<false><<<dim3((unsigned)nb_m, (h1 + 63) / 64), 512, 0, s>>>(
+            w.mlp_in, nullptr, mlp_w0, mlp_b0, batch, S, h1, IN, w.z1, w.z1part);
     }
     col_stats_kernel<<<dim3(gs, (h1 + 3) / 4), 256, 0, s>>>(w.z1part, bps, (int)nb_m, h1, batch, S,
                                                             nullptr, w.z1stats);
@@ -2494,19 +2420,18 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
         const int NT2 = din_mlp2_nt(h2);
         const int KS2 = (h1 + DIN_E - 1) / DIN_E;
         const int gp = (int)std::min<int64_t>(((int64_t)KS2 * NT2 * 64 + 255) / 256, 512);
-        const size_t lds = (size_t)KS2 * NT2 * 2048 + (size_t)4 * NT2 * 16 * 16;
+        // packed W1 (KS x NT x 2 KB) + the epilogue's column sums
+        auto mlp2_lds = [](int ks, int nt) { return (size_t)ks * nt * 2048 + (size_t)4 * nt * 16 * 16; };
         const unsigned g2 = (unsigned)std::min<int64_t>((batch + MLP1_ROWS - 1) / MLP1_ROWS, 512);
-#define NRK_MLP2(NTV)                                                                                   \
-    do {                                                                                                \
-        din_w1_pack_kernel<NTV><<<gp, 256, 0, s>>>(mlp_w1, h2, h1, w2max, w.w2pack);                     \
-        (void)hipFuncSetAttribute((const void*)din_mlp2_kernel<NTV>,                                     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
-        din_mlp2_kernel<NTV><<<g2, 256, lds, s>>>(w.z1, w.z1stats, z1max, w2max,                         \
-                                                  reinterpret_cast<const din_u4*>(w.w2pack), mlp_b1,     \
-                                                  batch, S, h1, h2, w.z2, w.z2part);                     \
-    } while (0)
-        if (NT2 == 2) NRK_MLP2(2); else if (NT2 == 4) NRK_MLP2(4); else if (NT2 == 5) NRK_MLP2(5); else NRK_MLP2(8);
-#undef NRK_MLP2
+        with_rung<2, 4, 5, 8>(NT2, [&](auto nt) {
+            constexpr int NTV = decltype(nt)::value;
+            din_w1_pack_kernel<NTV><<<gp, 256, 0, s>>>(mlp_w1, h2, h1, w2max, w.w2pack);
+            static std::atomic<uint64_t> lds_set{0};
+            lds_limit_once(lds_set, (const void*)din_mlp2_kernel<NTV>, mlp2_lds(256 / DIN_E, NTV));  // h1 <= 256
+            din_mlp2_kernel<NTV><<<g2, 256, mlp2_lds(KS2, NTV), s>>>(
+                w.z1, w.z1stats, z1max, w2max, reinterpret_cast<const din_u4*>(w.w2pack), mlp_b1, batch, S, h1, h2,
+                w.z2, w.z2part);
+        });
     } else {
         din_gemm_kernel<true><<<dim3((unsigned)nb_m, (h2 + 63) / 64), 512, 0, s>>>(
             w.z1, w.z1stats, mlp_w1, mlp_b1, batch, S, h2, h1, w.z2, w.z2part);

@@ -109,6 +109,8 @@ def synth_batch(rng, B, T, vocab_u, vocab_i, vocab_c, p_empty=0.05):
         (257, 128, 2, 3, 128, 64),
         (1000, 50, 4, 11, 200, 80),
         (5000, 33, 4, 16, 256, 100),
+        (130, 20, 2, 3, 64, 144),   # fast attention + MLP1, general second layer (h2 > 128)
+        (130, 20, 2, 3, 272, 48),   # T <= 64 with the general MLP (h1 > 256)
     ],
 )
 @pytest.mark.parametrize("table_dtype", ["fp32", "bf16"])
