@@ -795,6 +795,41 @@ __device__ __forceinline__ bool cf_prunable(const CfEnt& cur, const CfEnt& x, in
     return !__any(cf_better(x.s, x.f, ts, tf));
 }
 
+// A wave's running top 64, best first, over the caller's cur / started /
+// lane.  References in this order, like the closures this replaced: the
+// kernels' code is the same only in this shape (a free function, by value or
+// by reference, or another member order moves it).
+struct CfTop64 {
+    bool& started;
+    CfEnt& cur;
+    const int& lane;
+    // top 64 of two best-first lists: cur[l] vs x[63 - l] -> bitonic, then clean
+    __device__ __forceinline__ void merge(CfEnt x) const {
+        const double ys = __shfl(x.s, 63 - lane, WAVE);
+        const int64_t yf = __shfl(x.f, 63 - lane, WAVE);
+        const int32_t yc = __shfl(x.c, 63 - lane, WAVE);
+        if (cf_better(ys, yf, cur.s, cur.f)) {
+            cur.s = ys;
+            cur.f = yf;
+            cur.c = yc;
+        }
+        cf_clean64(cur);
+    }
+    __device__ void add(CfEnt x) const {  // x unsorted: the first one starts the list
+        cf_sort64(x);
+        if (!started) {
+            cur = x;
+            started = true;
+            return;
+        }
+        merge(x);
+    }
+    __device__ void push(CfEnt x, int n) const {  // a chunk of a source whose top n is wanted
+        if (started && cf_prunable(cur, x, n)) return;
+        add(x);
+    }
+};
+
 __global__ __launch_bounds__(256) void cf_topn_kernel(const int64_t* __restrict__ row_off, int64_t n_rows,
                                                     const int32_t* __restrict__ cols,
                                                     const double* __restrict__ vals,
@@ -823,7 +858,8 @@ __global__ __launch_bounds__(256) void cf_topn_kernel(const int64_t* __restrict_
             if (c0 == 0) {
                 cur = x;
             } else {
-                // top 64 of two sorted lists: cur[l] vs x[63 - l] -> bitonic, then clean
+                // CfTop64::merge, open-coded: through the struct (or any helper
+                // taking cur by reference) this kernel's selects become branches
                 const double ys = __shfl(x.s, 63 - lane, WAVE);
                 const int64_t yf = __shfl(x.f, 63 - lane, WAVE);
                 const int32_t yc = __shfl(x.c, 63 - lane, WAVE);
@@ -835,6 +871,7 @@ __global__ __launch_bounds__(256) void cf_topn_kernel(const int64_t* __restrict_
                 cf_clean64(cur);
             }
         }
+        // (the row is written here and in cf_topn_heavy_kernel: a shared writer moves both kernels' code)
         const int64_t m = n < topn ? n : topn;
         if (lane < topn) {
             const bool ok = lane < m;
@@ -1019,6 +1056,35 @@ __device__ __forceinline__ int64_t rc_lower(const int32_t* __restrict__ oq, int6
     return lo;
 }
 
+constexpr int64_t RC_HOT_FIRST = (int64_t)1 << 62;  // a hot fill's first slot: after every candidate (insertion order)
+
+// The lanes (as a ballot) whose popular item h (has: the lane holds one) may
+// fill the row (:116-122): not in the history and not yet ranked (in_cands(h):
+// h is one of the n_cands candidates, only asked when there are some).  The
+// history is read 64 clicks at a time, one per lane, each compared by a
+// uniform-index read (round 5: every lane walked the history by dependent
+// loads).  Every lane of the wave calls this, whatever its `has'.  Used by
+// rc_finish_small and rc_topk_wide_kernel; rc_finish_query keeps its own copy
+// (through this one rc_query_kernel's code moves) and rc_gen_query its form
+// with the first 64 clicks in a register.  No __restrict__ here: its scope
+// marks move the callers' code.
+template <class Count, class InCands>
+__device__ __forceinline__ uint64_t rc_hot_accept(int32_t h, bool has, Count n_cands, InCands&& in_cands, int64_t b,
+                                                  int64_t L, const int32_t* items) {
+    const int lane = threadIdx.x & 63;
+    bool ok = has;
+    for (int64_t hc = 0; hc < L; hc += 64) {
+        const int32_t hv = hc + lane < L ? items[b + hc + lane] : -1;
+        const int nh = (int)(L - hc < 64 ? L - hc : 64);
+        for (int l = 0; l < nh; ++l) {
+            const int32_t hl = __shfl(hv, l, WAVE);  // every lane active: a shuffle under
+            ok = ok && hl != h;                      // a short-circuit reads stale lanes
+        }
+    }
+    if (ok && n_cands > 0) ok = !in_cands(h);
+    return __builtin_amdgcn_ballot_w64(ok);
+}
+
 // The end of one query's recall (itemcf_recaller.py:116-129): the top-k
 // (k <= 64) of its distinct candidates by (score desc, first slot asc) --
 // chunk(c0) gives each lane its entry of positions [c0, c0 + 64) of a source
@@ -1032,32 +1098,14 @@ __device__ __forceinline__ void rc_finish_query(int64_t q, int64_t nsrc, Chunk&&
                                                 int32_t* __restrict__ out_items, double* __restrict__ out_scores,
                                                 int32_t* __restrict__ out_src, int32_t* __restrict__ out_cnt) {
     const int lane = threadIdx.x & 63;
-    const int64_t HOT_FIRST = (int64_t)1 << 62;  // after every candidate (insertion order)
     CfEnt cur{-INFINITY, INT64_MAX, -1};
     bool started = false;
-    auto merge = [&](CfEnt x) {
-        cf_sort64(x);
-        if (!started) {
-            cur = x;
-            started = true;
-            return;
-        }
-        const double ys = __shfl(x.s, 63 - lane, WAVE);
-        const int64_t yf = __shfl(x.f, 63 - lane, WAVE);
-        const int32_t yc = __shfl(x.c, 63 - lane, WAVE);
-        if (cf_better(ys, yf, cur.s, cur.f)) {
-            cur.s = ys;
-            cur.f = yf;
-            cur.c = yc;
-        }
-        cf_clean64(cur);
-    };
+    const CfTop64 top{started, cur, lane};
     int64_t n = 0;  // distinct candidates
     for (int64_t c0 = 0; c0 < nsrc; c0 += 64) {
         const CfEnt x = chunk(c0);
         n += __popcll(__ballot(x.c >= 0));
-        if (started && cf_prunable(cur, x, topk)) continue;
-        merge(x);
+        top.push(x, topk);
     }
     int64_t total = n;
     if (n < topk) {
@@ -1070,9 +1118,8 @@ __device__ __forceinline__ void rc_finish_query(int64_t q, int64_t nsrc, Chunk&&
             const int x = x0 + lane;
             const int32_t h = x < n_hot ? hot[x] : -1;
             bool ok = x < n_hot;
-            // not in the history: its clicks 64 at a time, one per lane, each
-            // compared by a uniform-index read (round 5: every lane walked the
-            // history by dependent loads)
+            // rc_hot_accept, open-coded: through it (alone, or with the rest
+            // of the fill in a helper) rc_query_kernel's code moves
             for (int64_t hc = 0; hc < L; hc += 64) {
                 const int32_t hv = hc + lane < L ? items[b + hc + lane] : -1;
                 const int nh = (int)(L - hc < 64 ? L - hc : 64);
@@ -1095,21 +1142,22 @@ __device__ __forceinline__ void rc_finish_query(int64_t q, int64_t nsrc, Chunk&&
             const int32_t hv = __shfl(h, src, WAVE);
             if (t >= 0 && t < take) {
                 hx.s = (double)(-(x0 + src) - 100);
-                hx.f = HOT_FIRST + x0 + src;
+                hx.f = RC_HOT_FIRST + x0 + src;
                 hx.c = hv;
             }
             got += take;
             need -= take;
         }
         total += got;
-        if (got > 0) merge(hx);
+        if (got > 0) top.add(hx);
     }
+    // (the row is written here and in rc_finish_small: a shared writer moves rc_topk's and rc_query's code)
     const int64_t m = total < topk ? total : topk;
     if (lane < topk) {
         const bool ok = lane < m;
         out_items[q * topk + lane] = ok ? cur.c : -1;
         out_scores[q * topk + lane] = ok ? cur.s : 0.0;
-        out_src[q * topk + lane] = ok ? (cur.f >= HOT_FIRST ? 1 : 0) : -1;
+        out_src[q * topk + lane] = ok ? (cur.f >= RC_HOT_FIRST ? 1 : 0) : -1;
     }
     if (lane == 0) out_cnt[q] = (int32_t)m;
 }
@@ -1127,6 +1175,19 @@ __device__ __forceinline__ void rc_cold(int64_t q, const int32_t* __restrict__ h
     }
     if (lane == 0) out_cnt[q] = m;
 }
+// (rc_cold past 64 lanes, for rc_topk_wide_kernel: a loop in rc_cold moves the topk <= 64 kernels' code)
+__device__ __forceinline__ void rc_cold_wide(int64_t q, const int32_t* __restrict__ hot, int n_hot, int topk,
+                                             int32_t* __restrict__ out_items, double* __restrict__ out_scores,
+                                             int32_t* __restrict__ out_src, int32_t* __restrict__ out_cnt) {
+    const int lane = threadIdx.x & 63;
+    const int m = n_hot < topk ? n_hot : topk;
+    for (int i = lane; i < topk; i += WAVE) {
+        out_items[q * topk + i] = i < m ? hot[i] : -1;
+        out_scores[q * topk + i] = i < m ? -(double)i : 0.0;
+        out_src[q * topk + i] = i < m ? 2 : -1;
+    }
+    if (lane == 0) out_cnt[q] = m;
+}
 
 // rc_finish_query for at most 64 distinct candidates, lane i < nd holding
 // entry x: the hot fill goes to lanes [nd, nd + got) (it only runs when nd <
@@ -1138,32 +1199,22 @@ __device__ __forceinline__ void rc_finish_small(int64_t q, CfEnt x, int nd, InCa
                                                 int32_t* __restrict__ out_items, double* __restrict__ out_scores,
                                                 int32_t* __restrict__ out_src, int32_t* __restrict__ out_cnt) {
     const int lane = threadIdx.x & 63;
-    const int64_t HOT_FIRST = (int64_t)1 << 62;
     int total = nd;
     if (nd < topk) {
         int need = topk - nd, got = 0;
         for (int x0 = 0; x0 < n_hot && need > 0; x0 += 64) {
             const int xi = x0 + lane;
             const int32_t h = xi < n_hot ? hot[xi] : -1;
-            bool ok = xi < n_hot;
-            for (int64_t hc = 0; hc < L; hc += 64) {
-                const int32_t hv = hc + lane < L ? items[b + hc + lane] : -1;
-                const int nh = (int)(L - hc < 64 ? L - hc : 64);
-                for (int l = 0; l < nh; ++l) {
-                    const int32_t hl = __shfl(hv, l, WAVE);  // every lane active: a shuffle under
-                    ok = ok && hl != h;                      // a short-circuit reads stale lanes
-                }
-            }
-            if (ok && nd > 0) ok = !in_cands(h);
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(ok);
+            const uint64_t bal = rc_hot_accept(h, xi < n_hot, nd, in_cands, b, L, items);
             const int take = __builtin_popcountll(bal) < need ? __builtin_popcountll(bal) : need;
+            // (the placement as in rc_finish_query, into lanes nd + got ..: as a helper it moves both kernels' code)
             const int t = lane - nd - got;
             int src = 0;
 #pragma unroll
             for (int st = 32; st >= 1; st >>= 1)
                 if (__builtin_popcountll(bal & ((2ull << (src + st - 1)) - 1ull)) < t + 1) src += st;
             const int32_t hv = __shfl(h, src, WAVE);
-            if (t >= 0 && t < take) x = CfEnt{(double)(-(x0 + src) - 100), HOT_FIRST + x0 + src, hv};
+            if (t >= 0 && t < take) x = CfEnt{(double)(-(x0 + src) - 100), RC_HOT_FIRST + x0 + src, hv};
             got += take;
             need -= take;
         }
@@ -1175,9 +1226,20 @@ __device__ __forceinline__ void rc_finish_small(int64_t q, CfEnt x, int nd, InCa
         const bool ok = lane < m;
         out_items[q * topk + lane] = ok ? x.c : -1;
         out_scores[q * topk + lane] = ok ? x.s : 0.0;
-        out_src[q * topk + lane] = ok ? (x.f >= HOT_FIRST ? 1 : 0) : -1;
+        out_src[q * topk + lane] = ok ? (x.f >= RC_HOT_FIRST ? 1 : 0) : -1;
     }
     if (lane == 0) out_cnt[q] = m;
+}
+
+// h is among the query's candidate items ej[a, e) (sorted): binary search
+__device__ __forceinline__ bool rc_has_item(const int32_t* __restrict__ ej, int64_t a, int64_t e, int32_t h) {
+    int64_t lo = a, hi = e;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ej[mid] < h) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < e && ej[lo] == h;
 }
 
 // The radix path's top-k: one wave per query over its emitted (q, j) run
@@ -1208,15 +1270,7 @@ __global__ __launch_bounds__(256) void rc_topk_kernel(
                 const int64_t i = a + c0 + (threadIdx.x & 63);
                 return i < e ? CfEnt{ev[i], ef[i], ej[i]} : CfEnt{-INFINITY, INT64_MAX, -1};
             },
-            [&](int32_t h) {  // binary search in the query's candidate js (sorted)
-                int64_t lo = a, hi = e;
-                while (lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (ej[mid] < h) lo = mid + 1;
-                    else hi = mid;
-                }
-                return lo < e && ej[lo] == h;
-            },
+            [&](int32_t h) { return rc_has_item(ej, a, e, h); },
             b, L, items, hot, n_hot, topk, out_items, out_scores, out_src, out_cnt);
     }
 }
@@ -1269,18 +1323,6 @@ __device__ __forceinline__ void wave_sort_u64(uint64_t (&k)[E]) {
             }
         }
     }
-}
-
-template <int E>
-__device__ __forceinline__ void rc_sort_lds(uint64_t* kw, int c) {
-    const int lane = threadIdx.x & 63;
-    uint64_t k[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) k[e] = e * 64 + lane < c ? kw[e * 64 + lane] : ~0ull;
-    wave_sort_u64<E>(k);
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (e * 64 + lane < c) kw[e * 64 + lane] = k[e];
 }
 
 // The recall of a query with at most RC_CAP candidates in one wave (round 6;
@@ -1472,18 +1514,8 @@ __global__ __launch_bounds__(1024) void cf_topn_heavy_kernel(const int64_t* __re
         const int64_t row = hrow[ih];
         const int64_t a = row_off[row], n = row_off[row + 1] - a;
         CfEnt cur{-INFINITY, INT64_MAX, -1};
-        auto merge_in = [&](CfEnt x) {  // x sorted desc; keep the top 64 of cur + x
-            const double ys = __shfl(x.s, 63 - lane, WAVE);
-            const int64_t yf = __shfl(x.f, 63 - lane, WAVE);
-            const int32_t yc = __shfl(x.c, 63 - lane, WAVE);
-            if (cf_better(ys, yf, cur.s, cur.f)) {
-                cur.s = ys;
-                cur.f = yf;
-                cur.c = yc;
-            }
-            cf_clean64(cur);
-        };
         bool started = false;
+        const CfTop64 top{started, cur, lane};
         // the wave's chunks wv, wv + 16, ... in that order, CF_HB of them
         // loaded at once (round 6: one chunk's loads per round trip, and most
         // chunks are pruned without a sort, so the loads were the time)
@@ -1507,7 +1539,7 @@ __global__ __launch_bounds__(1024) void cf_topn_heavy_kernel(const int64_t* __re
                 if (started && cf_prunable(cur, x, topn)) continue;
                 cf_sort64(x);
                 if (!started) cur = x;
-                else merge_in(x);
+                else top.merge(x);
                 started = true;
             }
         }
@@ -1516,7 +1548,7 @@ __global__ __launch_bounds__(1024) void cf_topn_heavy_kernel(const int64_t* __re
         lc[wv][lane] = cur.c;
         __syncthreads();
         if (wv == 0) {
-            for (int w = 1; w < 16; ++w) merge_in(CfEnt{ls[w][lane], lf[w][lane], lc[w][lane]});
+            for (int w = 1; w < 16; ++w) top.merge(CfEnt{ls[w][lane], lf[w][lane], lc[w][lane]});
             const int64_t m = n < topn ? n : topn;
             if (lane < topn) {
                 const bool ok = lane < m;
@@ -1539,26 +1571,6 @@ __global__ __launch_bounds__(1024) void cf_topn_heavy_kernel(const int64_t* __re
 // lands behind it and the 2K are re-sorted by an LDS bitonic sort on
 // (score desc, first asc) -- a total order, so the result does not depend on
 // the chunking.
-__device__ inline void cf_lds_sort(CfEnt* x, int n) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    wave_sync_lds();
-    for (int sz = 2; sz <= n; sz <<= 1) {
-        for (int st = sz >> 1; st > 0; st >>= 1) {
-            for (int i = lane; i < n / 2; i += WAVE) {
-                const int lo = 2 * st * (i / st) + (i % st), hi = lo + st;
-                const bool up = (lo & sz) == 0;
-                const CfEnt a = x[lo], b = x[hi];
-                const bool b_first = cf_better(b.s, b.f, a.s, a.f);
-                if (up ? b_first : !b_first && (a.s != b.s || a.f != b.f)) {
-                    x[lo] = b;
-                    x[hi] = a;
-                }
-            }
-            wave_sync_lds();
-        }
-    }
-}
-
 template <class Get>
 __device__ inline void cf_wave_topk(CfEnt* buf, int K, int64_t n, Get get) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -1566,7 +1578,7 @@ __device__ inline void cf_wave_topk(CfEnt* buf, int K, int64_t n, Get get) {
     for (int64_t c0 = 0; c0 < n; c0 += K) {
         wave_sync_lds();
         for (int i = lane; i < K; i += WAVE) buf[K + i] = c0 + i < n ? get(c0 + i) : CfEnt{-INFINITY, INT64_MAX, -1};
-        cf_lds_sort(buf, 2 * K);
+        wave_lds_sort(buf, 2 * K, [](const CfEnt& a, const CfEnt& b) { return cf_better(a.s, a.f, b.s, b.f); });
     }
     wave_sync_lds();
 }
@@ -1614,14 +1626,8 @@ __global__ __launch_bounds__(64) void rc_topk_wide_kernel(
         int32_t* oi = out_items + q * topk;
         double* os = out_scores + q * topk;
         int32_t* osrc = out_src + q * topk;
-        if (sl < 0) {  // cold start: [(hot[i], -i) for i < topk] (:68-70)
-            const int m = n_hot < topk ? n_hot : topk;
-            for (int i = lane; i < topk; i += WAVE) {
-                oi[i] = i < m ? hot[i] : -1;
-                os[i] = i < m ? -(double)i : 0.0;
-                osrc[i] = i < m ? 2 : -1;
-            }
-            if (lane == 0) out_cnt[q] = m;
+        if (sl < 0) {
+            rc_cold_wide(q, hot, n_hot, topk, out_items, out_scores, out_src, out_cnt);
             continue;
         }
         const int64_t a = rc_lower(eq, ne, q), e = rc_lower(eq, ne, q + 1), n = e - a;
@@ -1638,25 +1644,11 @@ __global__ __launch_bounds__(64) void rc_topk_wide_kernel(
             int need = topk - mc;
             for (int x0 = 0; x0 < n_hot && need > 0; x0 += WAVE) {
                 const int x = x0 + lane;
-                bool ok = false;
-                int32_t hv = -1;
-                if (x < n_hot) {
-                    hv = hot[x];
-                    ok = true;
-                    for (int64_t l = 0; l < L && ok; ++l) ok = items[b + l] != hv;
-                    if (ok && n > 0) {  // binary search in the query's candidate js (sorted)
-                        int64_t lo = a, hi = e;
-                        while (lo < hi) {
-                            const int64_t mid = (lo + hi) >> 1;
-                            if (ej[mid] < hv) lo = mid + 1;
-                            else hi = mid;
-                        }
-                        ok = !(lo < e && ej[lo] == hv);
-                    }
-                }
-                const unsigned long long bal = __ballot(ok);
+                const int32_t hv = x < n_hot ? hot[x] : -1;
+                const uint64_t bal = rc_hot_accept(
+                    hv, x < n_hot, n, [&](int32_t h) { return rc_has_item(ej, a, e, h); }, b, L, items);
                 const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-                if (ok && rank < need) {
+                if (((bal >> lane) & 1) && rank < need) {
                     oi[mc + got + rank] = hv;
                     os[mc + got + rank] = (double)(-x - 100);
                     osrc[mc + got + rank] = 1;
@@ -1712,26 +1704,36 @@ struct CfWs {
 
 static inline size_t cf_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// 256-byte-aligned bump allocation over a workspace (a null base: sizes only)
+struct CfBump {
+    uint8_t* p;
+    size_t o;
+    template <class T>
+    T* take(size_t bytes) {
+        T* r = reinterpret_cast<T*>(p + o);
+        o += cf_al(bytes);
+        return r;
+    }
+};
+
 static CfWs cf_ws_layout(void* base, int64_t P) {
     CfWs w;
-    uint8_t* p = reinterpret_cast<uint8_t*>(base);
-    size_t o = 0;
+    CfBump a{reinterpret_cast<uint8_t*>(base), 0};
     const size_t n = (size_t)(P > 0 ? P : 1);
     const size_t nblk = (n + RS_TILE - 1) / RS_TILE;
-    auto take = [&](size_t b) { uint8_t* r = p + o; o += cf_al(b); return r; };
-    w.ka = (uint64_t*)take(n * 8);
-    w.kb = (uint64_t*)take(n * 8);
-    w.va = (int32_t*)take(n * 4);
-    w.vb = (int32_t*)take(n * 4);
-    w.w = (double*)take(n * 8);
-    w.counts = (uint32_t*)take(256 * nblk * 4);
-    w.totals = (uint32_t*)take(256 * 4);
-    w.blkcnt = (uint32_t*)take(nblk * 4);
-    w.blkoff = (uint32_t*)take(nblk * 4);
-    w.tail = (double*)take(nblk * 8);
-    w.carry = (double*)take(nblk * 8);
-    w.brk = (int32_t*)take(nblk * 4);
-    w.bytes = o;
+    w.ka = a.take<uint64_t>(n * 8);
+    w.kb = a.take<uint64_t>(n * 8);
+    w.va = a.take<int32_t>(n * 4);
+    w.vb = a.take<int32_t>(n * 4);
+    w.w = a.take<double>(n * 8);
+    w.counts = a.take<uint32_t>(256 * nblk * 4);
+    w.totals = a.take<uint32_t>(256 * 4);
+    w.blkcnt = a.take<uint32_t>(nblk * 4);
+    w.blkoff = a.take<uint32_t>(nblk * 4);
+    w.tail = a.take<double>(nblk * 8);
+    w.carry = a.take<double>(nblk * 8);
+    w.brk = a.take<int32_t>(nblk * 4);
+    w.bytes = a.o;
     return w;
 }
 
@@ -1749,19 +1751,17 @@ struct RcWs {
 static RcWs rc_ws_layout(void* base, int64_t n_cand) {
     RcWs w;
     w.sort = cf_ws_layout(base, n_cand);
-    uint8_t* p = reinterpret_cast<uint8_t*>(base);
-    size_t o = w.sort.bytes;
+    CfBump a{reinterpret_cast<uint8_t*>(base), w.sort.bytes};
     const size_t n = (size_t)(n_cand > 0 ? n_cand : 1);
-    auto take = [&](size_t b) { uint8_t* r = p + o; o += cf_al(b); return r; };
-    w.eq = (int32_t*)take(n * 4);
-    w.ej = (int32_t*)take(n * 4);
-    w.ev = (double*)take(n * 8);
-    w.ef = (int64_t*)take(n * 8);
-    w.n_emit = (int64_t*)take(8);
-    w.hlist = (int2*)take((n / RC_CAP + 1) * sizeof(int2));  // at most n / (RC_CAP + 1) overflow queries
-    w.hcnt = (int32_t*)take(16);                              // + the overflow candidate total at +8
+    w.eq = a.take<int32_t>(n * 4);
+    w.ej = a.take<int32_t>(n * 4);
+    w.ev = a.take<double>(n * 8);
+    w.ef = a.take<int64_t>(n * 8);
+    w.n_emit = a.take<int64_t>(8);
+    w.hlist = a.take<int2>((n / RC_CAP + 1) * sizeof(int2));  // at most n / (RC_CAP + 1) overflow queries
+    w.hcnt = a.take<int32_t>(16);                              // + the overflow candidate total at +8
     w.htot = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(w.hcnt) + 8);
-    w.bytes = o;
+    w.bytes = a.o;
     return w;
 }
 
@@ -1775,6 +1775,63 @@ static inline int cf_wide_k(int k) {
     int p = 64;
     while (p < k) p <<= 1;
     return p;
+}
+
+// The sort keys: (i << bj | j) over nbits bits, and the all-ones sentinel of
+// the entries that are dropped (i == j; an item of the query's own history).
+struct CfKeys {
+    int bj, nbits;
+    uint64_t sentinel;
+};
+static inline uint64_t cf_sentinel(int nbits) { return nbits >= 64 ? ~0ull : (1ull << nbits) - 1; }
+// similarity, (i, j): 2^bj > n_items, so i = 2^bj - 1 is never an item
+static inline CfKeys cf_sim_keys(int32_t n_items) {
+    const int bj = bits_for(n_items);
+    return CfKeys{bj, 2 * bj, cf_sentinel(2 * bj)};
+}
+// recall, (q, j); nbits > 64: n_query * n_items does not fit a key
+static inline CfKeys rc_keys(int32_t n_items, int64_t n_query) {
+    const int bj = bits_for(n_items), nbits = bj + bits_for(n_query);
+    return CfKeys{bj, nbits, cf_sentinel(nbits)};
+}
+
+static inline CfParams cf_params(double loc_alpha, double loc_alpha_rev, double loc_beta, double time_alpha,
+                                 double created_alpha) {
+    return CfParams{loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha, cf_dt_zero(time_alpha),
+                    cf_ln(time_alpha), cf_ln(created_alpha)};
+}
+
+static inline int cf_grid(int64_t blocks, int64_t cap = 65536) { return (int)(blocks < cap ? blocks : cap); }
+
+// The stable radix sort of n > 0 (key, slot) pairs over nbits key bits, then
+// one (i, j, sum, first slot) entry per distinct key other than the sentinel,
+// *out_n of them: the sums of w[slot] in slot order, over sqrt(cnt_i cnt_j)
+// when item_cnt is given; the first slot through `slots' when given.  The
+// pairs are in (ws.ka, ws.va), or in (ws.kb, ws.vb) when in_b (rc_compact's
+// output); n_dev: their count on the device, n its bound.
+static void cf_sort_reduce(const CfWs& ws, bool in_b, int64_t n, const CfKeys& k, const double* w,
+                           const unsigned long long* item_cnt, const int32_t* slots, const int64_t* n_dev,
+                           int32_t* out_i, int32_t* out_j, double* out_v, int64_t* out_first, int64_t* out_n,
+                           hipStream_t s) {
+    const int nblk = (int)((n + RS_TILE - 1) / RS_TILE);
+    uint64_t* kin = in_b ? ws.kb : ws.ka;
+    uint64_t* kout = in_b ? ws.ka : ws.kb;
+    int32_t* vin = in_b ? ws.vb : ws.va;
+    int32_t* vout = in_b ? ws.va : ws.vb;
+    for (int shift = 0; shift < k.nbits; shift += 8) {
+        rs_upsweep<<<nblk, RS_THREADS, 0, s>>>(kin, n, shift, nblk, ws.counts, n_dev);
+        rs_scan_rows<<<256, 256, 0, s>>>(ws.counts, nblk, ws.totals);
+        rs_downsweep<<<nblk, RS_THREADS, 0, s>>>(kin, vin, kout, vout, n, shift, nblk, ws.counts, ws.totals, n_dev);
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+    }
+    double* wsorted = reinterpret_cast<double*>(kout);  // the free ping-pong key buffer
+    cf_tile_reduce<<<nblk, RS_THREADS, 0, s>>>(kin, vin, w, n, k.sentinel, ws.blkcnt, ws.tail, ws.brk, wsorted,
+                                               n_dev);
+    cf_head_scan<<<1, 1024, 0, s>>>(ws.blkcnt, nblk, ws.blkoff, out_n);
+    cf_carry_scan<<<1, 1024, 0, s>>>(ws.tail, ws.brk, nblk, ws.carry);
+    cf_emit<<<nblk, RS_THREADS, 0, s>>>(kin, vin, wsorted, n, k.sentinel, ws.blkoff, ws.carry, item_cnt, slots, k.bj,
+                                        out_i, out_j, out_v, out_first, n_dev);
 }
 
 }  // namespace nrk
@@ -1793,8 +1850,7 @@ int nrk_itemcf_pair_offsets(const int64_t* offsets, int64_t n_users, int64_t* pa
     return NRK_OK;
 }
 
-size_t nrk_itemcf_workspace_bytes(int64_t n_pairs, int32_t n_items) {
-    (void)n_items;
+size_t nrk_itemcf_workspace_bytes(int64_t n_pairs, int32_t /*n_items*/) {
     if (n_pairs < 0) return 0;
     return cf_ws_layout(nullptr, n_pairs).bytes;
 }
@@ -1815,44 +1871,20 @@ int nrk_itemcf_sim(const int64_t* offsets, int64_t n_users, const int32_t* items
     const CfWs w = cf_ws_layout(workspace, n_pairs);
     NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
     hipStream_t s = as_stream(stream);
-    const int bj = bits_for(n_items);  // 2^bj > n_items - 1 + 1: i = 2^bj - 1 is never an item
-    const int nbits = 2 * bj;
-    const uint64_t sentinel = (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1);
+    const CfKeys k = cf_sim_keys(n_items);
     (void)hipMemsetAsync(out_cnt, 0, sizeof(int64_t) * (size_t)n_items, s);
-    const CfParams prm{loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha, cf_dt_zero(time_alpha),
-                       cf_ln(time_alpha), cf_ln(created_alpha)};
-    const int64_t pgrid = (n_pairs + 4 * CF_CHUNK - 1) / (4 * CF_CHUNK);
+    const CfParams prm = cf_params(loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha);
     if (n_users > 0 && n_pairs > 0)
-        cf_pairs_flat_kernel<<<(int)(pgrid < 8192 ? pgrid : 8192), 256, 0, s>>>(
-            offsets, n_users, items, ts, created, pair_off, 0, prm, bj, sentinel, w.ka, w.va, w.w);
+        cf_pairs_flat_kernel<<<cf_grid((n_pairs + 4 * CF_CHUNK - 1) / (4 * CF_CHUNK), 8192), 256, 0, s>>>(
+            offsets, n_users, items, ts, created, pair_off, 0, prm, k.bj, k.sentinel, w.ka, w.va, w.w);
     if (n_users > 0)
         cf_item_count_kernel<<<1024, CF_CNT_THREADS, 0, s>>>(offsets, n_users, items,
                                                              reinterpret_cast<unsigned long long*>(out_cnt));
-    const int64_t n = n_pairs;
-    const int nblk = (int)((n + RS_TILE - 1) / RS_TILE);
-    uint64_t* kin = w.ka;
-    uint64_t* kout = w.kb;
-    int32_t* vin = w.va;
-    int32_t* vout = w.vb;
-    if (n > 0) {
-        for (int shift = 0; shift < nbits; shift += 8) {
-            rs_upsweep<<<nblk, RS_THREADS, 0, s>>>(kin, n, shift, nblk, w.counts);
-            rs_scan_rows<<<256, 256, 0, s>>>(w.counts, nblk, w.totals);
-            rs_downsweep<<<nblk, RS_THREADS, 0, s>>>(kin, vin, kout, vout, n, shift, nblk, w.counts,
-                                                     w.totals);
-            uint64_t* tk = kin; kin = kout; kout = tk;
-            int32_t* tv = vin; vin = vout; vout = tv;
-        }
-        double* wsorted = reinterpret_cast<double*>(kout);  // the free ping-pong key buffer
-        cf_tile_reduce<<<nblk, RS_THREADS, 0, s>>>(kin, vin, w.w, n, sentinel, w.blkcnt, w.tail, w.brk, wsorted);
-        cf_head_scan<<<1, 1024, 0, s>>>(w.blkcnt, nblk, w.blkoff, out_n);
-        cf_carry_scan<<<1, 1024, 0, s>>>(w.tail, w.brk, nblk, w.carry);
-        cf_emit<<<nblk, RS_THREADS, 0, s>>>(kin, vin, wsorted, n, sentinel, w.blkoff, w.carry,
-                                             reinterpret_cast<const unsigned long long*>(out_cnt), nullptr,
-                                             bj, out_i, out_j, out_v, out_first);
-    } else {
+    if (n_pairs > 0)
+        cf_sort_reduce(w, false, n_pairs, k, w.w, reinterpret_cast<const unsigned long long*>(out_cnt), nullptr,
+                       nullptr, out_i, out_j, out_v, out_first, out_n, s);
+    else
         (void)hipMemsetAsync(out_n, 0, sizeof(int64_t), s);
-    }
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -1872,16 +1904,14 @@ int nrk_itemcf_topn(const int64_t* row_off, int64_t n_rows, const int32_t* cols,
         const size_t lds = (size_t)2 * K * sizeof(CfEnt);
         (void)hipFuncSetAttribute((const void*)cf_topn_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
-        cf_topn_wide_kernel<<<(int)(n_rows < 65536 ? n_rows : 65536), 64, lds, as_stream(stream)>>>(
+        cf_topn_wide_kernel<<<cf_grid(n_rows), 64, lds, as_stream(stream)>>>(
             row_off, n_rows, cols, vals, first, topn, K, out_cols, out_vals, out_cnt);
         NRK_CHECK_LAUNCH();
         return NRK_OK;
     }
-    const int64_t g = (n_rows + 3) / 4;
-    cf_topn_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(
+    cf_topn_kernel<<<cf_grid((n_rows + 3) / 4), 256, 0, as_stream(stream)>>>(
         row_off, n_rows, cols, vals, first, topn, out_cols, out_vals, out_cnt);
-    const int64_t gw = (n_rows + 1023) / 1024;
-    cf_topn_heavy_kernel<<<(int)(gw < 512 ? gw : 512), 1024, 0, as_stream(stream)>>>(
+    cf_topn_heavy_kernel<<<cf_grid((n_rows + 1023) / 1024, 512), 1024, 0, as_stream(stream)>>>(
         row_off, n_rows, cols, vals, first, topn, out_cols, out_vals, out_cnt);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -1896,9 +1926,7 @@ int nrk_itemcf_recall_offsets(const int64_t* q_slot, int64_t n_query, const int6
     hipStream_t s = as_stream(stream);
     if (n_query > 0) {
         NRK_REQUIRE(q_slot && offsets && items && nbr_cnt, "null pointer");
-        const int64_t g = (n_query + 3) / 4;
-        rc_count_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cnt,
-                                                                     cand_off);
+        rc_count_kernel<<<cf_grid((n_query + 3) / 4), 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cnt, cand_off);
     }
     scan_exclusive_kernel<ScanVals><<<1, 1024, 0, s>>>(ScanVals{cand_off}, n_query, cand_off);
     NRK_CHECK_LAUNCH();
@@ -1934,13 +1962,11 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
     RcBack bk;
     if (!rc_back_buffers(workspace, n_query, n_items, n_cand, &bk))
         NRK_UNSUPPORTED("n_query * n_items too large for 64-bit keys");
-    const int64_t g = (n_query + 3) / 4;
-    const int gq = (int)(g < 65536 ? g : 65536);
     const RcParams prm{loc_beta, created_alpha, cf_ln(created_alpha), topn, ke, bk.bj};
     if (n_cand > 0)
-        rc_cand_kernel<<<gq, 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created,
-                                          emb_cols, emb_vals, emb_cnt, prm, cand_off, bk.sentinel, bk.keys,
-                                          bk.slots, bk.contrib);
+        rc_cand_kernel<<<cf_grid((n_query + 3) / 4), 256, 0, s>>>(
+            q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created, emb_cols, emb_vals, emb_cnt, prm,
+            cand_off, bk.sentinel, bk.keys, bk.slots, bk.contrib);
     return rc_back_finish(q_slot, n_query, offsets, items, n_items, hot, n_hot, cand_off, n_cand, topk, out_items,
                           out_scores, out_src, out_cnt, workspace, s);
 }
@@ -1953,10 +1979,9 @@ size_t rc_back_bytes(int64_t n_cand) { return rc_ws_layout(nullptr, n_cand).byte
 
 bool rc_back_buffers(void* workspace, int64_t n_query, int32_t n_items, int64_t n_cand, RcBack* out) {
     const RcWs w = rc_ws_layout(workspace, n_cand);
-    const int bj = bits_for(n_items);
-    const int nbits = bj + bits_for(n_query);
-    if (nbits > 64) return false;
-    *out = RcBack{w.sort.ka, w.sort.va, w.sort.w, (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1), bj};
+    const CfKeys k = rc_keys(n_items, n_query);
+    if (k.nbits > 64) return false;
+    *out = RcBack{w.sort.ka, w.sort.va, w.sort.w, k.sentinel, k.bj};
     return true;
 }
 
@@ -1971,26 +1996,18 @@ int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offset
                    int32_t* out_items, double* out_scores, int32_t* out_src, int32_t* out_cnt, void* workspace,
                    hipStream_t s) {
     const RcWs w = rc_ws_layout(workspace, n_cand);
-    const int bj = bits_for(n_items);
-    const int nbits = bj + bits_for(n_query);
-    const uint64_t sentinel = (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1);
+    const CfKeys k = rc_keys(n_items, n_query);
     const int64_t g = (n_query + 3) / 4;
-    const int gq = (int)(g < 65536 ? g : 65536);
     const int64_t n = n_cand;
-    const int nblk = (int)((n + RS_TILE - 1) / RS_TILE);
     // topk <= 64: every query with <= RC_CAP candidates is finished by
     // rc_query_kernel from rc_cand's output; the radix path then runs over
     // the listed larger queries only, compacted to the front of the sort
     // buffers (device-side count: its launches exit at once when there are
     // none).  topk > 64: every query takes the radix path.
     const bool fused = topk <= 64;
-    const int64_t* n_dev = nullptr;
-    int gl = gq;
+    int gl = cf_grid(g);  // rc_topk's grid: every query, or the listed ones
     if (n > 0) {
-        uint64_t* kin = w.sort.ka;
-        uint64_t* kout = w.sort.kb;
-        int32_t* vin = w.sort.va;
-        int32_t* vout = w.sort.vb;
+        const int64_t* n_dev = nullptr;
         if (fused) {
             (void)hipMemsetAsync(w.hcnt, 0, 16, s);
             static const int qgrid = [] {
@@ -2003,53 +2020,34 @@ int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offset
                     per = 4;
                 return per * (cu > 0 ? cu : 256);
             }();
-            rc_query_kernel<<<(int)(g < qgrid ? g : qgrid), 256, 0, s>>>(
-                q_slot, n_query, offsets, items, cand_off, w.sort.ka, w.sort.w, sentinel, bj, hot, n_hot, topk,
+            rc_query_kernel<<<cf_grid(g, qgrid), 256, 0, s>>>(
+                q_slot, n_query, offsets, items, cand_off, w.sort.ka, w.sort.w, k.sentinel, k.bj, hot, n_hot, topk,
                 out_items, out_scores, out_src, out_cnt, w.hlist, w.hcnt, w.htot);
-            const int64_t gh = (n / (RC_CAP + 1) + 4) / 4;
-            gl = (int)(gh < 65536 ? gh : 65536);
-            rc_compact_kernel<<<gl, 256, 0, s>>>(cand_off, kin, vin, w.hlist, w.hcnt, kout, vout);
-            uint64_t* tk = kin; kin = kout; kout = tk;
-            int32_t* tv = vin; vin = vout; vout = tv;
+            gl = cf_grid((n / (RC_CAP + 1) + 4) / 4);
+            rc_compact_kernel<<<gl, 256, 0, s>>>(cand_off, w.sort.ka, w.sort.va, w.hlist, w.hcnt, w.sort.kb,
+                                                 w.sort.vb);
             n_dev = reinterpret_cast<const int64_t*>(w.htot);
         }
-        for (int shift = 0; shift < nbits; shift += 8) {
-            rs_upsweep<<<nblk, RS_THREADS, 0, s>>>(kin, n, shift, nblk, w.sort.counts, n_dev);
-            rs_scan_rows<<<256, 256, 0, s>>>(w.sort.counts, nblk, w.sort.totals);
-            rs_downsweep<<<nblk, RS_THREADS, 0, s>>>(kin, vin, kout, vout, n, shift, nblk, w.sort.counts,
-                                                     w.sort.totals, n_dev);
-            uint64_t* tk = kin; kin = kout; kout = tk;
-            int32_t* tv = vin; vin = vout; vout = tv;
-        }
-        double* wsorted = reinterpret_cast<double*>(kout);
-        cf_tile_reduce<<<nblk, RS_THREADS, 0, s>>>(kin, vin, w.sort.w, n, sentinel, w.sort.blkcnt, w.sort.tail,
-                                                   w.sort.brk, wsorted, n_dev);
-        cf_head_scan<<<1, 1024, 0, s>>>(w.sort.blkcnt, nblk, w.sort.blkoff, w.n_emit);
-        cf_carry_scan<<<1, 1024, 0, s>>>(w.sort.tail, w.sort.brk, nblk, w.sort.carry);
-        cf_emit<<<nblk, RS_THREADS, 0, s>>>(kin, vin, wsorted, n, sentinel, w.sort.blkoff, w.sort.carry, nullptr,
-                                             nullptr, bj, w.eq, w.ej, w.ev, w.ef, n_dev);
+        cf_sort_reduce(w.sort, fused, n, k, w.sort.w, nullptr, nullptr, n_dev, w.eq, w.ej, w.ev, w.ef, w.n_emit, s);
     } else {
         (void)hipMemsetAsync(w.n_emit, 0, sizeof(int64_t), s);
         if (fused) (void)hipMemsetAsync(w.hcnt, 0, 16, s);
     }
     if (fused) {
         // n == 0: no listed queries, every query is a cold start or has no
-        // candidates -> all of them through the list-free form
-        if (n > 0)
-            rc_topk_kernel<<<gl, 256, 0, s>>>(q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej, w.ev, w.ef,
-                                              w.n_emit, topk, out_items, out_scores, out_src, out_cnt, w.hlist,
-                                              w.hcnt);
-        else
-            rc_topk_kernel<<<gq, 256, 0, s>>>(q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej, w.ev, w.ef,
-                                              w.n_emit, topk, out_items, out_scores, out_src, out_cnt);
+        // candidates -> all of them through the list-free form (null lists)
+        const bool listed = n > 0;
+        rc_topk_kernel<<<gl, 256, 0, s>>>(q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej, w.ev, w.ef,
+                                          w.n_emit, topk, out_items, out_scores, out_src, out_cnt,
+                                          listed ? w.hlist : nullptr, listed ? w.hcnt : nullptr);
     } else {
         const int K = cf_wide_k(topk);
         const size_t lds = (size_t)2 * K * sizeof(CfEnt);
         (void)hipFuncSetAttribute((const void*)rc_topk_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
-        rc_topk_wide_kernel<<<(int)(n_query < 65536 ? n_query : 65536), 64, lds, s>>>(
-            q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej, w.ev, w.ef, w.n_emit, topk, K, out_items,
-            out_scores, out_src, out_cnt);
+        rc_topk_wide_kernel<<<cf_grid(n_query), 64, lds, s>>>(q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej,
+                                                              w.ev, w.ef, w.n_emit, topk, K, out_items, out_scores,
+                                                              out_src, out_cnt);
     }
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -2063,8 +2061,7 @@ int nrk_itemcf_row_offsets(const int32_t* ei, int64_t n, int64_t n_rows, int64_t
     clear_error();
     NRK_REQUIRE(n >= 0 && n_rows >= 0, "negative size");
     NRK_REQUIRE(row_off && (n == 0 || ei), "null pointer");
-    const int64_t g = (n_rows + 1 + 255) / 256;
-    cf_row_offsets_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(ei, n, n_rows, row_off);
+    cf_row_offsets_kernel<<<cf_grid((n_rows + 1 + 255) / 256), 256, 0, as_stream(stream)>>>(ei, n, n_rows, row_off);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -2078,15 +2075,12 @@ int nrk_itemcf_pairs(const int64_t* offsets, int64_t n_users, const int32_t* ite
     NRK_REQUIRE(n_users >= 0 && slot_base >= 0 && n_items >= 1, "bad sizes");
     if (n_users == 0) return NRK_OK;
     NRK_REQUIRE(offsets && items && ts && created && pair_off && keys && slots && w && item_cnt, "null pointer");
-    const int bj = bits_for(n_items);
-    const int nbits = 2 * bj;
-    const uint64_t sentinel = (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1);
-    const CfParams prm{loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha, cf_dt_zero(time_alpha),
-                       cf_ln(time_alpha), cf_ln(created_alpha)};
+    const CfKeys k = cf_sim_keys(n_items);
+    const CfParams prm = cf_params(loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha);
     // (the pair count lives on the device, pair_off[n_users]: a fixed
     // persistent grid walks it)
     cf_pairs_flat_kernel<<<2048, 256, 0, as_stream(stream)>>>(
-        offsets, n_users, items, ts, created, pair_off, slot_base, prm, bj, sentinel, keys, slots, w);
+        offsets, n_users, items, ts, created, pair_off, slot_base, prm, k.bj, k.sentinel, keys, slots, w);
     cf_item_count_kernel<<<1024, CF_CNT_THREADS, 0, as_stream(stream)>>>(
         offsets, n_users, items, reinterpret_cast<unsigned long long*>(item_cnt));
     NRK_CHECK_LAUNCH();
@@ -2115,30 +2109,9 @@ int nrk_itemcf_reduce(const uint64_t* keys, const int32_t* slots, const double* 
     NRK_REQUIRE(keys && slots && w && item_cnt && out_i && out_j && out_v && out_first, "null pointer");
     const CfWs ws = cf_ws_layout(workspace, n);
     NRK_REQUIRE(workspace_bytes >= ws.bytes, "workspace too small");
-    const int bj = bits_for(n_items);
-    const int nbits = 2 * bj;
-    const uint64_t sentinel = (nbits >= 64) ? ~0ull : ((1ull << nbits) - 1);
-    const int nblk = (int)((n + RS_TILE - 1) / RS_TILE);
-    const int64_t g = (n + 255) / 256;
-    cf_iota_copy_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, s>>>(keys, n, ws.ka, ws.va);
-    uint64_t* kin = ws.ka;
-    uint64_t* kout = ws.kb;
-    int32_t* vin = ws.va;
-    int32_t* vout = ws.vb;
-    for (int shift = 0; shift < nbits; shift += 8) {
-        rs_upsweep<<<nblk, RS_THREADS, 0, s>>>(kin, n, shift, nblk, ws.counts);
-        rs_scan_rows<<<256, 256, 0, s>>>(ws.counts, nblk, ws.totals);
-        rs_downsweep<<<nblk, RS_THREADS, 0, s>>>(kin, vin, kout, vout, n, shift, nblk, ws.counts, ws.totals);
-        uint64_t* tk = kin; kin = kout; kout = tk;
-        int32_t* tv = vin; vin = vout; vout = tv;
-    }
-    double* wsorted = reinterpret_cast<double*>(kout);
-    cf_tile_reduce<<<nblk, RS_THREADS, 0, s>>>(kin, vin, w, n, sentinel, ws.blkcnt, ws.tail, ws.brk, wsorted);
-    cf_head_scan<<<1, 1024, 0, s>>>(ws.blkcnt, nblk, ws.blkoff, out_n);
-    cf_carry_scan<<<1, 1024, 0, s>>>(ws.tail, ws.brk, nblk, ws.carry);
-    cf_emit<<<nblk, RS_THREADS, 0, s>>>(kin, vin, wsorted, n, sentinel, ws.blkoff, ws.carry,
-                                         reinterpret_cast<const unsigned long long*>(item_cnt), slots, bj,
-                                         out_i, out_j, out_v, out_first);
+    cf_iota_copy_kernel<<<cf_grid((n + 255) / 256), 256, 0, s>>>(keys, n, ws.ka, ws.va);
+    cf_sort_reduce(ws, false, n, cf_sim_keys(n_items), w, reinterpret_cast<const unsigned long long*>(item_cnt), slots,
+                   nullptr, out_i, out_j, out_v, out_first, out_n, s);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }

@@ -166,10 +166,12 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Wave-cooperative bitonic sort of n candidates (a power of two) held in
-// this wave's LDS region, best first.  Run-time loops (nothing unrolled):
-// the large-list path of the merge / bound / fusion kernels.
-__device__ inline void wave_lds_sort(Cand* x, int n) {
+// Wave-cooperative bitonic sort of n entries (a power of two) held in this
+// wave's LDS region, best first: first(a, b) is true when a goes before b (a
+// strict total order).  Run-time loops (nothing unrolled): the large-list
+// path of the merge / bound / fusion kernels and of the wide ItemCF top-k.
+template <class T, class First>
+__device__ inline void wave_lds_sort(T* x, int n, First first) {
     const int lane = threadIdx.x & (WAVE - 1);
     wave_sync_lds();
     for (int sz = 2; sz <= n; sz <<= 1) {
@@ -177,8 +179,8 @@ __device__ inline void wave_lds_sort(Cand* x, int n) {
             for (int i = lane; i < n / 2; i += WAVE) {
                 const int lo = 2 * st * (i / st) + (i % st), hi = lo + st;
                 const bool up = (lo & sz) == 0;
-                const Cand a = x[lo], b = x[hi];
-                if (up ? better(b, a) : better(a, b)) {
+                const T a = x[lo], b = x[hi];
+                if (up ? first(b, a) : first(a, b)) {
                     x[lo] = b;
                     x[hi] = a;
                 }
@@ -186,6 +188,9 @@ __device__ inline void wave_lds_sort(Cand* x, int n) {
             wave_sync_lds();
         }
     }
+}
+__device__ inline void wave_lds_sort(Cand* x, int n) {
+    wave_lds_sort(x, n, [](const Cand& a, const Cand& b) { return better(a, b); });
 }
 
 __device__ __forceinline__ float wave_sum_f32(float v) {

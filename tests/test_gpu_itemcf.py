@@ -94,11 +94,12 @@ def test_itemcf_recall_matches_reference(golden):
             np.testing.assert_allclose([b for _, b in got], g["recall_scores"][ro[n]:ro[n + 1]], rtol=RTOL)
 
 
-def _random_lists(rng, n_users, n_items, max_len, repeat_p=0.1):
+def _random_lists(rng, n_users, n_items, max_len, repeat_p=0.1, click_items=None):
+    """click_items: clicks are drawn from item ids [0, click_items) (default: all n_items)."""
     L = rng.integers(0, max_len + 1, n_users)
     offs = np.zeros(n_users + 1, np.int64)
     offs[1:] = np.cumsum(L)
-    items = rng.integers(0, n_items, offs[-1]).astype(np.int32)
+    items = rng.integers(0, n_items if click_items is None else click_items, offs[-1]).astype(np.int32)
     rep = rng.random(offs[-1]) < repeat_p  # repeated clicks on the previous item
     rep[offs[:-1][L > 0]] = False
     idx = np.nonzero(rep)[0]
@@ -235,10 +236,10 @@ def test_itemcf_recall_with_embedding_content_weight_matches_reference(golden):
     assert all(isinstance(s, int) for _, s in cold)
 
 
-def _recall_case(rng, n_users, n_items, max_len, topn, n_hot):
+def _recall_case(rng, n_users, n_items, max_len, topn, n_hot, click_items=None):
     from nrk import ops
 
-    offs, items, ts, created = _random_lists(rng, n_users, n_items, max_len)
+    offs, items, ts, created = _random_lists(rng, n_users, n_items, max_len, click_items=click_items)
     sim = _gpu_sim(offs, items, ts, created, n_items)
     nc, nv, nn = ops.itemcf_topn(sim.row_offsets(), sim.j, sim.v, sim.first, topn)
     hot = rng.permutation(n_items)[:n_hot].astype(np.int32)
@@ -269,6 +270,47 @@ def test_itemcf_recall_vs_oracle(n_users, n_items, max_len, topn, topk, n_hot):
         assert np.array_equal(gi[r, :m], oi[r, :m]), r
         np.testing.assert_allclose(gs[r, :m], os_[r, :m], rtol=RTOL, atol=0)
         assert (gsrc[r, :m] == 2).all() if q[r] < 0 else (gsrc[r, :m] < 2).all()
+
+
+@pytest.mark.parametrize("topk", [64, 100])
+@pytest.mark.parametrize("n_users,max_len", [(40, 40), (20, 150)])
+def test_itemcf_recall_hot_fill_after_many_candidates(n_users, max_len, topk):
+    """The hot fill of queries that take the radix path: more than RC_CAP = 512
+    candidates, yet fewer than topk distinct ones.  Clicks come from item ids
+    [0, 50) of 120 and the hot list is 100 of all 120 ids, so unclicked hot
+    items exist to fill with.  Checked like test_itemcf_recall_vs_oracle; the
+    preconditions (candidate counts, fills, long histories, an exhausted hot
+    list) are asserted from the host data."""
+    from nrk import ops
+
+    n_items, click_items, topn, n_hot = 120, 50, 20, 100
+    rng = np.random.default_rng(2024)
+    offs, items, created, nc, nv, nn, hot = _recall_case(rng, n_users, n_items, max_len, topn, n_hot,
+                                                         click_items=click_items)
+    q = np.concatenate([np.arange(n_users), [-1, -1]]).astype(np.int64)  # all users + two cold-start queries
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    gi, gs, gsrc, gn = ops.itemcf_recall(d(q), d(offs), d(items), nc, nv, nn, d(created), d(hot), topk)
+    nn_h = nn.cpu().numpy()
+    oi, os_, on = oracle.itemcf_recall(q, offs, items, nc.cpu().numpy(), nv.cpu().numpy(), nn_h, created, hot, topk,
+                                       n_items)
+    gi, gs, gsrc, gn = (t.cpu().numpy() for t in (gi, gs, gsrc, gn))
+    assert np.array_equal(gn, on)
+    for r in range(len(q)):
+        m = on[r]
+        assert np.array_equal(gi[r, :m], oi[r, :m]), r
+        np.testing.assert_allclose(gs[r, :m], os_[r, :m], rtol=RTOL, atol=0)
+        assert (gsrc[r, :m] == 2).all() if q[r] < 0 else (gsrc[r, :m] < 2).all()
+        # a fill scores -x - 100, a candidate a product of positive weights
+        assert q[r] < 0 or np.array_equal(gsrc[r, :m] == 1, os_[r, :m] <= -100.0), r
+    # the preconditions: C_q = sum of nbr_cnt over the history; hot-filled = some src == 1
+    hist_len = np.diff(offs)
+    c_q = np.array([nn_h[items[offs[u]:offs[u + 1]]].sum() for u in range(n_users)])
+    filled = np.array([(gsrc[u, :on[u]] == 1).any() for u in range(n_users)])
+    assert (filled & (c_q > 512)).any()
+    if max_len == 150:
+        assert (filled & (c_q > 512) & (hist_len > 64)).any()
+        if topk == 100:
+            assert (filled & (on[:n_users] < topk)).any()  # the hot list ran out
 
 
 def test_itemcf_recall_full_size():
