@@ -508,6 +508,44 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
                              float* out_probs, float* out_logits, void* workspace,
                              size_t workspace_bytes, nrk_stream_t stream);
 
+/* DIN training (DINRanker.train's loop body, src/rank/DIN.py:907-912): one
+ * batch of DINModel.forward in train mode, mean BCELoss and the backward,
+ * all fp32.  Table, row_base, index tensors and mask as nrk_din_forward;
+ * labels [batch] fp32, 0 or 1.  weights is one packed vector in the order
+ *   att_w0 [36, 4*n_item*32] | att_b0 [36] | att_w1 [36] | att_b1 [1] |
+ *   mlp_w0 [h1, in] | mlp_b0 [h1] | mlp_w1 [h2, h1] | mlp_b1 [h2] |
+ *   mlp_w2 [h2] | mlp_b2 [1]
+ * and w_grad its dense gradient (the Dice alphas have none).  Built for
+ * dim == 32, fp32 tables (table_dtype 0), Dice (activation 0), n_item in
+ * {1, 2, 4, 8}, n_user in [1, 64], n_ctx in [0, 64], h1 and h2 in [1, 1024],
+ * batch in [2, 8192], seq_len in [1, 128]; anything else is NRK_EUNSUPPORTED
+ * before a pointer is touched (the workspace query then returns 0).
+ *   loss     device float: the mean over the batch
+ *   t_rows / t_vals / t_count   gradient of the concatenated table as a
+ *            compact list: *t_count ascending unique rows, t_vals
+ *            [*t_count, 32]; capacity min(n_table_rows, batch *
+ *            (n_user + n_ctx + n_item * (1 + seq_len))) rows.  Candidate and
+ *            history contributions of an item table meet in the same rows.
+ * Masked positions carry gradient through the Dice statistics of their
+ * columns (into row 0 of every item table among others).  Every output is
+ * bitwise reproducible.  No host synchronisation. */
+size_t nrk_din_train_workspace_bytes(int64_t n_table_rows, int dim, int table_dtype, int n_user, int n_item,
+                                     int n_ctx, int h1, int h2, int activation, int64_t batch, int seq_len);
+int nrk_din_train_grad(const float* table, int64_t n_table_rows, int dim, int table_dtype, const int64_t* row_base,
+                       int n_user, int n_item, int n_ctx, const float* weights, int h1, int h2, int activation,
+                       const int32_t* user_idx, const int32_t* item_idx, const int32_t* hist_idx,
+                       const int32_t* ctx_idx, const float* mask, const float* labels, int64_t batch, int seq_len,
+                       float* loss, float* w_grad, int32_t* t_rows, float* t_vals, int32_t* t_count, void* workspace,
+                       size_t workspace_bytes, nrk_stream_t stream);
+
+/* One torch.optim.Adam step with dense semantics over the packed weights
+ * and the whole table (as nrk_tt_adam_step): rows absent from the list have
+ * g = 0 and still move; a row with m = v = g = 0 is left untouched. */
+int nrk_din_adam_step(float* weights, float* w_m, float* w_v, const float* w_grad, int64_t n_weights, float* table,
+                      float* t_m, float* t_v, int64_t n_table_rows, int dim, const int32_t* t_rows,
+                      const float* t_vals, const int32_t* t_count, double lr, double beta1, double beta2, double eps,
+                      int64_t t, nrk_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
 /* Recall -> rank hand-off (fused config 5)                               */
 /* ---------------------------------------------------------------------- */

@@ -1,0 +1,1071 @@
+// din_train.hip -- one DIN training step on gfx950: DINModel.forward in
+// train mode (src/rank/DIN.py:214-286), mean BCELoss, the whole backward, a
+// bitwise-reproducible reduction of the embedding gradients and a
+// dense-semantics Adam sweep (DINRanker.train's loop body, DIN.py:907-912).
+// Everything stored is fp32 and nothing is shared with the inference forward
+// (din.hip: no split-fp16 products here).  Long sums are blocked: a block's
+// products are added in fp32, the blocks, the batch / history / contribution
+// sums and the Dice statistics in fp64, rounded once.
+//
+// A Dice layer normalises with the statistics of the batch, and they carry
+// gradient, so both directions split into phases at every Dice:
+//   forward   dt_att_fwd      z[b,t,h] = W [k, q, q-k, q*k] + b in the folded
+//                             form (W_k - W_d) k + (W_q + W_d) q + W_p (q*k):
+//                             per sample W_eff = (W_k - W_d) + W_p q in LDS
+//             dt_colstat      mean and unbiased std of every (t,h) column
+//             dt_att_out      Dice, Linear(36 -> 1), mask, sum_t w k, and the
+//                             MLP input row [user | ctx | candidate | history]
+//             dt_gemm / dt_colstat / dt_dice_fwd, twice; dt_head (loss)
+//   backward  dt_dice_sums + dt_dice_bwd per MLP Dice, dt_gemm for dW / dA
+//             dt_att_ds       d score[b,t]
+//             dt_dice_sums    the two column sums of the attention Dice
+//             dt_att_bwd      d z (in place), d k, d q, and per block the
+//                             partial sums of dz^T k and dz^T (q*k)
+//             dt_att_final    partials in block order -> d att_w0
+//   tables    dt_emb_keys, a stable radix sort of (row, contribution) pairs
+//             (rocprim), dt_emb_heads/starts, dt_emb_piece, dt_emb_long: every
+//             destination row is the sum of its contributions in ascending
+//             contribution order, pieces of 512 first, then the pieces in
+//             order, so a pad row with 10^5 terms is a 512-term chain and a
+//             chain over its ~200 pieces, never one thread over all of them.
+// A masked position contributes nothing through w * mask but does through
+// the mean and std of its (t,h) columns; no kernel skips it.
+// Every sum has a fixed order and no output is written by a floating-point
+// atomic: the same call twice gives the same bits.
+//
+// The matrix products run on the vector ALUs in 64 x 64 LDS tiles
+// (dt_gemm_kernel), not yet on v_mfma_f32_32x32x2_f32.
+//
+// Out of contract: a Dice column whose batch std is exactly 0 (torch's own
+// gradient is NaN there; the std term is dropped here), and |logit| so large
+// that p (1 - p) underflows in BCELoss (|x| >~ 15).  Loss and gradients stay
+// finite in both cases; parity with torch is not claimed.
+//
+// tr_adam of tower_train.hip is restated here (dt_adam) rather than shared
+// through a header, so that tower_train.hip compiles exactly as before.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "din_common.h"
+
+namespace nrk {
+
+constexpr int DT_MAXT = 128, DT_MAXB = 8192, DT_MAXH = 1024, DT_MAXF = 64;
+constexpr int DT_PIECE = 512;  // contributions one 32-lane group sums in a chain
+constexpr int DT_CB = 8;       // samples per dt_att_bwd block
+constexpr double DT_EPS = 1e-8;
+
+struct DtIdx {
+    const float* table;
+    const int64_t* row_base;
+    const int32_t *user, *item, *hist, *ctx;
+    const float* mask;
+    int Fu, Fc, B, T;
+};
+
+// Dice (DIN.py:39-44): p = sigmoid((x - mean) / (std + eps)), y = p x + (1 - p) 0.01 x.
+// The statistics, p and the backward's combination are formed in fp64: with a
+// small batch the three terms of the backward cancel (at B = 2 the normalised
+// value does not depend on x at all), and fp32 statistics would leave their
+// own rounding, multiplied by dz / std, in the result.
+__device__ __forceinline__ double dt_dice_p(float x, double mu, double sd) {
+    return 1.0 / (1.0 + exp(-((double)x - mu) / (sd + DT_EPS)));
+}
+__device__ __forceinline__ float dt_dice(float x, double mu, double sd) {
+    const double p = dt_dice_p(x, mu, sd);
+    return (float)(p * x + (1.0 - p) * 0.01 * x);
+}
+
+// d x of one Dice element given the upstream g and its column's two sums
+// (s1 = sum_b dz / (std + eps), s2 = sum_b dz (x - mean) / (std + eps)^2)
+__device__ __forceinline__ float dt_dice_dx(float x, double mu, double sd, float g, double s1, double s2, int B) {
+    const double den = sd + DT_EPS, xc = (double)x - mu;
+    const double p = dt_dice_p(x, mu, sd);
+    const double dz = 0.99 * g * x * (p * (1.0 - p));
+    const double direct = g * (p + 0.01 * (1.0 - p));
+    const double via_sd = sd > 0.0 ? s2 * xc / ((double)(B - 1) * sd) : 0.0;
+    return (float)(direct + dz / den - s1 / (double)B - via_sd);
+}
+
+// ------------------------------------------------------------ tiled GEMM --
+// C[m, n] = sum_k A(m, k) Bm(k, n) (+ bias[n]), A(m, k) = A[m sam + k sak],
+// Bm(k, n) = Bm[k sbk + n sbn]; k ascending.  gridDim.z > 1 splits k into
+// slices of kper whose results go to part[z][M][N] (dt_sum_parts adds them in
+// slice order).
+struct DtGemm {
+    const float *A, *Bm, *bias;
+    float* C;
+    double* part;
+    int64_t sam, sak, sbk, sbn;
+    int M, N, K, ldc, kper;
+};
+
+__global__ __launch_bounds__(256) void dt_gemm_kernel(DtGemm g) {
+    __shared__ float As[16][68], Bs[16][68];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const int k0 = blockIdx.z * g.kper, k1 = min(g.K, k0 + g.kper);
+    // a tile's 16 products are added in fp32, the tiles in fp64: the error of a
+    // long k stays that of a blocked sum, not of one fp32 chain
+    double acc[4][4] = {};
+    for (int kb = k0; kb < k1; kb += 16) {
+        for (int i = tid; i < 1024; i += 256) {
+            int mm, kk;
+            if (g.sak == 1) {
+                kk = i & 15;
+                mm = i >> 4;
+            } else {
+                mm = i & 63;
+                kk = i >> 6;
+            }
+            const int m = m0 + mm, k = kb + kk;
+            As[kk][mm] = (m < g.M && k < k1) ? g.A[m * g.sam + k * g.sak] : 0.0f;
+        }
+        for (int i = tid; i < 1024; i += 256) {
+            int nn, kk;
+            if (g.sbk == 1) {
+                kk = i & 15;
+                nn = i >> 4;
+            } else {
+                nn = i & 63;
+                kk = i >> 6;
+            }
+            const int n = n0 + nn, k = kb + kk;
+            Bs[kk][nn] = (n < g.N && k < k1) ? g.Bm[k * g.sbk + n * g.sbn] : 0.0f;
+        }
+        __syncthreads();
+        float tile[4][4] = {};
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            float a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a[i] = As[kk][ty * 4 + i];
+                b[i] = Bs[kk][tx * 4 + i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tile[i][j] = fmaf(a[i], b[j], tile[i][j]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] += (double)tile[i][j];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int m = m0 + ty * 4 + i, n = n0 + tx * 4 + j;
+            if (m < g.M && n < g.N) {
+                if (gridDim.z == 1) g.C[(int64_t)m * g.ldc + n] = (float)(acc[i][j] + (g.bias ? (double)g.bias[n] : 0.0));
+                else g.part[((int64_t)blockIdx.z * g.M + m) * g.N + n] = acc[i][j];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dt_sum_parts_kernel(const double* __restrict__ part, int S, int M, int N,
+                                                           int ldc, float* __restrict__ C) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * N) return;
+    double t = 0.0;
+    for (int s = 0; s < S; ++s) t += part[(int64_t)s * M * N + i];
+    C[(int64_t)(i / N) * ldc + i % N] = (float)t;
+}
+
+// ------------------------------------------------------- column reductions --
+// Block = 16 columns x 64 row slices (rows ascending inside a slice), the 64
+// partials added in slice order.
+template <class F>
+__device__ __forceinline__ F dt_col_combine(F (*part)[16], F s) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    part[tid >> 4][tid & 15] = s;
+    __syncthreads();
+    F t = 0;
+    for (int r = 0; r < 64; ++r) t += part[r][tid & 15];
+    return t;  // every thread of a column holds the column's sum
+}
+
+// out[c] = sum_b x[b, c]
+__global__ __launch_bounds__(1024) void dt_colsum_kernel(const float* __restrict__ x, int B, int C,
+                                                         float* __restrict__ out) {
+    __shared__ double part[64][16];
+    const int tid = threadIdx.x, c = blockIdx.x * 16 + (tid & 15), r = tid >> 4;
+    const int per = (B + 63) / 64, b0 = min(B, r * per), b1 = min(B, b0 + per);
+    double s = 0.0;
+    if (c < C)
+        for (int b = b0; b < b1; ++b) s += (double)x[(int64_t)b * C + c];
+    s = dt_col_combine(part, s);
+    if (r == 0 && c < C) out[c] = (float)s;
+}
+
+// mean and unbiased std (torch.std) of every column of x [B, C], in fp64
+__global__ __launch_bounds__(1024) void dt_colstat_kernel(const float* __restrict__ x, int B, int C,
+                                                          double* __restrict__ mu, double* __restrict__ sd) {
+    __shared__ double part[64][16];
+    const int tid = threadIdx.x, c = blockIdx.x * 16 + (tid & 15), r = tid >> 4;
+    const int per = (B + 63) / 64, b0 = min(B, r * per), b1 = min(B, b0 + per);
+    double s = 0.0;
+    if (c < C)
+        for (int b = b0; b < b1; ++b) s += (double)x[(int64_t)b * C + c];
+    const double m = dt_col_combine(part, s) / (double)B;
+    s = 0.0;
+    if (c < C)
+        for (int b = b0; b < b1; ++b) {
+            const double d = (double)x[(int64_t)b * C + c] - m;
+            s += d * d;
+        }
+    s = dt_col_combine(part, s);
+    if (r == 0 && c < C) {
+        mu[c] = m;
+        sd[c] = sqrt(s / (double)(B - 1));
+    }
+}
+
+// The column sums of a Dice backward over x [B, C] with upstream
+// g[b, c] = G[b gs + c / gdiv] * (w ? w[c % gdiv] : 1):
+//   S[0][c] = sum_b dz / (std + eps), S[1][c] = sum_b dz (x - mean) / (std + eps)^2,
+//   S[2][c] = sum_b G[b, c / gdiv] * dice(x)   (d of the weight w)
+__global__ __launch_bounds__(1024) void dt_dice_sums_kernel(const float* __restrict__ x,
+                                                            const double* __restrict__ mu,
+                                                            const double* __restrict__ sd,
+                                                            const float* __restrict__ G, int gs, int gdiv,
+                                                            const float* __restrict__ w, int B, int C,
+                                                            double* __restrict__ S) {
+    __shared__ double part[64][16];
+    const int tid = threadIdx.x, c = blockIdx.x * 16 + (tid & 15), r = tid >> 4;
+    const int per = (B + 63) / 64, b0 = min(B, r * per), b1 = min(B, b0 + per);
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (c < C) {
+        const double m = mu[c], sdc = sd[c], den = sdc + DT_EPS;
+        const float wv = w ? w[c % gdiv] : 1.0f;
+        const int gc = c / gdiv;
+        for (int b = b0; b < b1; ++b) {
+            const float xv = x[(int64_t)b * C + c], g0 = G[(int64_t)b * gs + gc], g = g0 * wv;
+            const double xc = (double)xv - m, p = dt_dice_p(xv, m, sdc);
+            const double dz = 0.99 * g * xv * (p * (1.0 - p));
+            s1 += dz / den;
+            s2 += dz * xc / (den * den);
+            s3 += (double)g0 * (p * xv + (1.0 - p) * 0.01 * xv);
+        }
+    }
+    s1 = dt_col_combine(part, s1);
+    s2 = dt_col_combine(part, s2);
+    s3 = dt_col_combine(part, s3);
+    if (r == 0 && c < C) {
+        S[c] = s1;
+        S[C + c] = s2;
+        S[2 * C + c] = s3;
+    }
+}
+
+__global__ __launch_bounds__(256) void dt_dice_fwd_kernel(const float* __restrict__ x, const double* __restrict__ mu,
+                                                          const double* __restrict__ sd, int64_t n, int C,
+                                                          float* __restrict__ y) {
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        y[i] = dt_dice(x[i], mu[c], sd[c]);
+    }
+}
+
+// g [B, C] (d of the Dice output) -> d of the Dice input, in place
+__global__ __launch_bounds__(256) void dt_dice_bwd_kernel(const float* __restrict__ x, const double* __restrict__ mu,
+                                                          const double* __restrict__ sd, const double* __restrict__ S,
+                                                          int B, int C, float* __restrict__ g) {
+    const int64_t n = (int64_t)B * C;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        g[i] = dt_dice_dx(x[i], mu[c], sd[c], g[i], S[c], S[C + c], B);
+    }
+}
+
+// ------------------------------------------------------------------- head --
+// One wave per sample: a2 = dice(z2), logit = w2 . a2 + b2, p = sigmoid,
+// BCELoss (log clamped at -100) and its gradient as torch forms it:
+// (p - y) / max((1 - p) p, 1e-12) / B, then sigmoid's (1 - p) p.
+// hb[b] = [g a2 | g] (column sums: d w2, d b2), da2[b] = g w2.
+__global__ __launch_bounds__(256) void dt_head_kernel(const float* __restrict__ z2, const double* __restrict__ mu,
+                                                      const double* __restrict__ sd, const float* __restrict__ w2,
+                                                      const float* __restrict__ b2, const float* __restrict__ label,
+                                                      int B, int H2, float* __restrict__ loss_b,
+                                                      float* __restrict__ hb, float* __restrict__ da2) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    double s = 0.0;
+    for (int c = lane; c < H2; c += WAVE) s += (double)w2[c] * (double)dt_dice(z2[(int64_t)b * H2 + c], mu[c], sd[c]);
+    const float logit = (float)(wave_sum_f64(s) + (double)b2[0]);
+    const float p = 1.0f / (1.0f + expf(-logit)), y = label[b];
+    if (lane == 0) loss_b[b] = -(y * fmaxf(logf(p), -100.0f) + (1.0f - y) * fmaxf(log1pf(-p), -100.0f));
+    const float gi = (1.0f / (float)B) * (p - y) / fmaxf((1.0f - p) * p, 1e-12f);
+    const float g = gi * (1.0f - p) * p;
+    for (int c = lane; c < H2; c += WAVE) {
+        hb[(int64_t)b * (H2 + 1) + c] = g * dt_dice(z2[(int64_t)b * H2 + c], mu[c], sd[c]);
+        da2[(int64_t)b * H2 + c] = g * w2[c];
+    }
+    if (lane == 0) hb[(int64_t)b * (H2 + 1) + H2] = g;
+}
+
+// mean of the per-sample losses: 16 slices, fixed tree (as tt_wgrad_kernel)
+__global__ __launch_bounds__(1024) void dt_loss_kernel(const float* __restrict__ loss_b, int B,
+                                                       float* __restrict__ loss) {
+    __shared__ double part[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per = (B + 15) / 16, b0 = min(B, wave * per), b1 = min(B, b0 + per);
+    double s = 0.0;
+    for (int b = b0 + lane; b < b1; b += WAVE) s += (double)loss_b[b];
+    s = wave_sum_f64(s);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < 16; ++k) t += part[k];
+        *loss = (float)(t / (double)B);
+    }
+}
+
+// -------------------------------------------------------------- attention --
+// Per-sample staging shared by the attention kernels: the candidate row q,
+// the absolute table rows of the history, and W_eff = (W_k - W_d) + W_p q
+// (row stride Di + 1: lanes of different h fall into different banks).
+template <int NI>
+__device__ __forceinline__ void dt_stage_sample(const DtIdx& ix, int b, float* q, int* hrow) {
+    constexpr int Di = NI * 32;
+    for (int d = threadIdx.x; d < Di; d += 256) {
+        const int f = d >> 5;
+        q[d] = ix.table[(ix.row_base[ix.Fu + f] + ix.item[(int64_t)b * NI + f]) * 32 + (d & 31)];
+    }
+    for (int i = threadIdx.x; i < ix.T * NI; i += 256)
+        hrow[i] = (int)(ix.row_base[ix.Fu + i % NI] + ix.hist[(int64_t)b * ix.T * NI + i]);
+}
+template <int NI>
+__device__ __forceinline__ void dt_build_weff(const float* __restrict__ W, const float* q, float* weff) {
+    constexpr int Di = NI * 32, WS = Di + 1;
+    for (int i = threadIdx.x; i < 36 * Di; i += 256) {
+        const int h = i / Di, d = i % Di;
+        const float* w = W + (size_t)h * 4 * Di;
+        weff[h * WS + d] = fmaf(w[3 * Di + d], q[d], w[d] - w[2 * Di + d]);
+    }
+}
+template <int NI>
+__device__ __forceinline__ float dt_k(const DtIdx& ix, const int* hrow, int t, int d) {
+    return ix.table[(int64_t)hrow[t * NI + (d >> 5)] * 32 + (d & 31)];
+}
+
+template <int NI>
+__global__ __launch_bounds__(256) void dt_att_fwd_kernel(DtIdx ix, const float* __restrict__ W,
+                                                         const float* __restrict__ b0, float* __restrict__ z) {
+    constexpr int Di = NI * 32, WS = Di + 1;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* weff = lds;
+    float* q = weff + 36 * WS;
+    float* c = q + Di;
+    int* hrow = reinterpret_cast<int*>(c + 36);
+    const int b = blockIdx.x, T = ix.T;
+    dt_stage_sample<NI>(ix, b, q, hrow);
+    __syncthreads();
+    dt_build_weff<NI>(W, q, weff);
+    if (threadIdx.x < 36) {
+        const float* w = W + (size_t)threadIdx.x * 4 * Di;
+        double acc = b0[threadIdx.x];
+        for (int d = 0; d < Di; ++d) acc += (double)(w[Di + d] + w[2 * Di + d]) * (double)q[d];
+        c[threadIdx.x] = (float)acc;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < T * 36; o += 256) {
+        const int t = o / 36, h = o % 36;
+        double acc = c[h];  // a feature's 32 products in fp32, the features in fp64
+        for (int f = 0; f < NI; ++f) {
+            const float4* kr = reinterpret_cast<const float4*>(ix.table + (int64_t)hrow[t * NI + f] * 32);
+            const float* wr = weff + h * WS + f * 32;
+            float part = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float4 kv = kr[e];
+                part = fmaf(wr[4 * e], kv.x, part);
+                part = fmaf(wr[4 * e + 1], kv.y, part);
+                part = fmaf(wr[4 * e + 2], kv.z, part);
+                part = fmaf(wr[4 * e + 3], kv.w, part);
+            }
+            acc += (double)part;
+        }
+        z[((int64_t)b * T) * 36 + o] = (float)acc;
+    }
+}
+
+// Dice, Linear(36 -> 1), mask, the weighted history and the MLP input row
+template <int NI>
+__global__ __launch_bounds__(256) void dt_att_out_kernel(DtIdx ix, const float* __restrict__ z,
+                                                         const double* __restrict__ mu, const double* __restrict__ sd,
+                                                         const float* __restrict__ w1, const float* __restrict__ b1,
+                                                         int IN, float* __restrict__ wbuf, float* __restrict__ x0) {
+    constexpr int Di = NI * 32;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* y = lds;                // [T][36]
+    float* s = y + ix.T * 36;      // [T]
+    float* q = s + ix.T;           // [Di]
+    int* hrow = reinterpret_cast<int*>(q + Di);
+    const int b = blockIdx.x, T = ix.T, Fu = ix.Fu, Fc = ix.Fc;
+    dt_stage_sample<NI>(ix, b, q, hrow);
+    for (int o = threadIdx.x; o < T * 36; o += 256) y[o] = dt_dice(z[(int64_t)b * T * 36 + o], mu[o], sd[o]);
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += 256) {
+        double a = b1[0];
+        for (int h = 0; h < 36; ++h) a += (double)w1[h] * (double)y[t * 36 + h];
+        const float acc = (float)a * ix.mask[(int64_t)b * T + t];
+        s[t] = acc;
+        wbuf[(int64_t)b * T + t] = acc;
+    }
+    __syncthreads();
+    float* xr = x0 + (int64_t)b * IN;
+    for (int i = threadIdx.x; i < (Fu + Fc) * 32; i += 256) {
+        const int f = i >> 5;
+        const int64_t row = f < Fu ? ix.row_base[f] + ix.user[(int64_t)b * Fu + f]
+                                   : ix.row_base[NI + f] + ix.ctx[(int64_t)b * Fc + (f - Fu)];
+        xr[i] = ix.table[row * 32 + (i & 31)];
+    }
+    for (int d = threadIdx.x; d < Di; d += 256) {
+        xr[(Fu + Fc) * 32 + d] = q[d];
+        double acc = 0.0;
+        for (int t = 0; t < T; ++t) acc += (double)s[t] * (double)dt_k<NI>(ix, hrow, t, d);
+        xr[(Fu + Fc) * 32 + Di + d] = (float)acc;
+    }
+}
+
+// d score[b, t] = mask * sum_d d wh[d] k[t, d]
+template <int NI>
+__global__ __launch_bounds__(256) void dt_att_ds_kernel(DtIdx ix, const float* __restrict__ dx0, int IN,
+                                                        float* __restrict__ ds) {
+    constexpr int Di = NI * 32;
+    __shared__ float dwh[Di];
+    __shared__ int hrow[DT_MAXT * NI];
+    const int b = blockIdx.x, T = ix.T;
+    for (int d = threadIdx.x; d < Di; d += 256) dwh[d] = dx0[(int64_t)b * IN + (ix.Fu + ix.Fc) * 32 + Di + d];
+    for (int i = threadIdx.x; i < T * NI; i += 256)
+        hrow[i] = (int)(ix.row_base[ix.Fu + i % NI] + ix.hist[(int64_t)b * T * NI + i]);
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += 256) {
+        double acc = 0.0;
+        for (int d = 0; d < Di; ++d) acc += (double)dwh[d] * (double)dt_k<NI>(ix, hrow, t, d);
+        ds[(int64_t)b * T + t] = (float)acc * ix.mask[(int64_t)b * T + t];
+    }
+}
+
+// DT_CB samples per block.  Per sample: d z[t,h] (written over z), A[h] =
+// sum_t dz, d k[t,d] = sum_h dz W_eff + w[t] d wh[d], U[h,d] = sum_t dz k,
+// d q[d] = sum_h A (W_q + W_d) + sum_h W_p U, added to the candidate part of
+// dx0.  Over the block's samples (ascending): sum U and sum q U in registers,
+// stored as gpart[block][2][36][Di].
+template <int NI>
+__global__ __launch_bounds__(256) void dt_att_bwd_kernel(DtIdx ix, const float* __restrict__ W,
+                                                         const float* __restrict__ w1, const double* __restrict__ mu,
+                                                         const double* __restrict__ sd, const double* __restrict__ S,
+                                                         const float* __restrict__ ds, const float* __restrict__ wbuf,
+                                                         int IN, float* __restrict__ z, float* __restrict__ dx0,
+                                                         float* __restrict__ dk, float* __restrict__ Abuf,
+                                                         double* __restrict__ gpart) {
+    constexpr int Di = NI * 32, WS = Di + 1, HG = 256 / Di, HPG = (36 + HG - 1) / HG;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* weff = lds;                 // [36][WS]
+    float* q = weff + 36 * WS;         // [Di]
+    float* dwh = q + Di;               // [Di]
+    float* uq = dwh + Di;              // [HG][Di] = 256
+    float* As = uq + 256;              // [36] (+4 pad)
+    float* wrow = As + 40;             // [T]
+    float* dzp = wrow + ix.T;          // [T][36]
+    int* hrow = reinterpret_cast<int*>(dzp + ix.T * 36);
+    const int T = ix.T, B = ix.B, C = T * 36, tid = threadIdx.x;
+    const int d_own = tid % Di, hg = tid / Di, cand = (ix.Fu + ix.Fc) * 32;
+    double gk[HPG], gp[HPG];
+#pragma unroll
+    for (int i = 0; i < HPG; ++i) gk[i] = gp[i] = 0.0;
+    for (int b = blockIdx.x * DT_CB; b < min(B, (int)(blockIdx.x + 1) * DT_CB); ++b) {
+        __syncthreads();  // the previous sample's LDS is no longer read
+        dt_stage_sample<NI>(ix, b, q, hrow);
+        for (int d = tid; d < Di; d += 256) dwh[d] = dx0[(int64_t)b * IN + cand + Di + d];
+        for (int t = tid; t < T; t += 256) wrow[t] = wbuf[(int64_t)b * T + t];
+        for (int o = tid; o < C; o += 256) {
+            const int64_t zi = (int64_t)b * C + o;
+            const float g = ds[(int64_t)b * T + o / 36] * w1[o % 36];
+            const float v = dt_dice_dx(z[zi], mu[o], sd[o], g, S[o], S[C + o], B);
+            dzp[o] = v;
+            z[zi] = v;
+        }
+        __syncthreads();
+        dt_build_weff<NI>(W, q, weff);
+        if (tid < 36) {
+            double a = 0.0;
+            for (int t = 0; t < T; ++t) a += (double)dzp[t * 36 + tid];
+            As[tid] = (float)a;
+            Abuf[(int64_t)b * 36 + tid] = (float)a;
+        }
+        float U[HPG];
+#pragma unroll
+        for (int i = 0; i < HPG; ++i) U[i] = 0.0f;
+        for (int t = 0; t < T; ++t) {
+            const float kv = dt_k<NI>(ix, hrow, t, d_own);
+#pragma unroll
+            for (int i = 0; i < HPG; ++i) {
+                const int h = hg * HPG + i;
+                if (h < 36) U[i] = fmaf(dzp[t * 36 + h], kv, U[i]);
+            }
+        }
+        {
+            float part = 0.0f;
+            const float qv = q[d_own];
+#pragma unroll
+            for (int i = 0; i < HPG; ++i) {
+                const int h = hg * HPG + i;
+                if (h < 36) {
+                    gk[i] += (double)U[i];
+                    gp[i] += (double)qv * (double)U[i];
+                    part = fmaf(W[(size_t)h * 4 * Di + 3 * Di + d_own], U[i], part);
+                }
+            }
+            uq[hg * Di + d_own] = part;
+        }
+        __syncthreads();  // weff, As, uq complete
+        for (int o = tid; o < T * Di; o += 256) {
+            const int t = o / Di, d = o % Di;
+            float acc = 0.0f;
+            for (int h = 0; h < 36; ++h) acc = fmaf(dzp[t * 36 + h], weff[h * WS + d], acc);
+            dk[((int64_t)b * T) * Di + o] = fmaf(wrow[t], dwh[d], acc);
+        }
+        if (tid < Di) {
+            double dq = 0.0;
+            for (int h = 0; h < 36; ++h) {
+                const float* w = W + (size_t)h * 4 * Di;
+                dq += (double)As[h] * (double)(w[Di + tid] + w[2 * Di + tid]);
+            }
+            for (int g = 0; g < HG; ++g) dq += (double)uq[g * Di + tid];
+            dx0[(int64_t)b * IN + cand + tid] = (float)((double)dx0[(int64_t)b * IN + cand + tid] + dq);
+        }
+    }
+    double* gp_out = gpart + (size_t)blockIdx.x * 2 * 36 * Di;
+#pragma unroll
+    for (int i = 0; i < HPG; ++i) {
+        const int h = hg * HPG + i;
+        if (h < 36) {
+            gp_out[h * Di + d_own] = gk[i];
+            gp_out[36 * Di + h * Di + d_own] = gp[i];
+        }
+    }
+}
+
+// d att_w0 [36, 4 Di] = [G_k | G_q | G_q - G_k | G_p], the block partials in
+// block order; d att_w1[h] = sum_t S3[t, h]; d att_b1 = sum_t dsT[t]
+__global__ __launch_bounds__(256) void dt_att_final_kernel(const double* __restrict__ gpart, int nblk, int Di,
+                                                           const float* __restrict__ Gq,
+                                                           const double* __restrict__ S3, const float* __restrict__ dsT,
+                                                           int T, float* __restrict__ g_w0, float* __restrict__ g_w1,
+                                                           float* __restrict__ g_b1) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 36 * Di) {
+        double gk = 0.0, gp = 0.0;
+        for (int k = 0; k < nblk; ++k) {
+            gk += gpart[(size_t)k * 2 * 36 * Di + i];
+            gp += gpart[(size_t)k * 2 * 36 * Di + 36 * Di + i];
+        }
+        const int h = i / Di, d = i % Di;
+        const double gq = Gq[i];
+        float* o = g_w0 + (size_t)h * 4 * Di;
+        o[d] = (float)gk;
+        o[Di + d] = (float)gq;
+        o[2 * Di + d] = (float)(gq - gk);
+        o[3 * Di + d] = (float)gp;
+    } else if (i < 36 * Di + 36) {
+        const int h = i - 36 * Di;
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += S3[t * 36 + h];
+        g_w1[h] = (float)s;
+    } else if (i == 36 * Di + 36) {
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += (double)dsT[t];
+        g_b1[0] = (float)s;
+    }
+}
+
+// ------------------------------------------------------ embedding gradients --
+// Contribution id = b * S + slot, slot over [user f | ctx f | candidate f |
+// history (t, f)], S = Fu + Fc + NI + T NI: the first Fu + Fc + NI slots are
+// 32-float pieces of dx0[b] in its own order, the rest of dk[b].
+__global__ __launch_bounds__(256) void dt_emb_keys_kernel(DtIdx ix, int NI, int64_t n, uint32_t* __restrict__ keys,
+                                                          int32_t* __restrict__ cid) {
+    const int Fu = ix.Fu, Fc = ix.Fc, T = ix.T, S = Fu + Fc + NI + T * NI;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / S;
+        const int s = (int)(i % S);
+        int64_t row;
+        if (s < Fu) row = ix.row_base[s] + ix.user[b * Fu + s];
+        else if (s < Fu + Fc) row = ix.row_base[NI + s] + ix.ctx[b * Fc + (s - Fu)];
+        else if (s < Fu + Fc + NI) row = ix.row_base[Fu + (s - Fu - Fc)] + ix.item[b * NI + (s - Fu - Fc)];
+        else {
+            const int j = s - Fu - Fc - NI;
+            row = ix.row_base[Fu + j % NI] + ix.hist[b * T * NI + j];
+        }
+        keys[i] = (uint32_t)row;
+        cid[i] = (int32_t)i;
+    }
+}
+
+__global__ __launch_bounds__(256) void dt_emb_heads_kernel(const uint32_t* __restrict__ keys, int64_t n,
+                                                           int32_t* __restrict__ flag) {
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        flag[i] = i == 0 || keys[i] != keys[i - 1];
+}
+
+// seg = inclusive scan of flag: segment index + 1 of every sorted position
+__global__ __launch_bounds__(256) void dt_emb_starts_kernel(const uint32_t* __restrict__ keys,
+                                                            const int32_t* __restrict__ flag,
+                                                            const int32_t* __restrict__ seg, int64_t n,
+                                                            int32_t* __restrict__ starts, int32_t* __restrict__ rows,
+                                                            int32_t* __restrict__ count) {
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        if (flag[i]) {
+            starts[seg[i] - 1] = (int32_t)i;
+            rows[seg[i] - 1] = (int32_t)keys[i];
+        }
+        if (i == n - 1) {
+            starts[seg[i]] = (int32_t)n;
+            *count = seg[i];
+        }
+    }
+}
+
+struct DtSrc {
+    const float *dx0, *dk;
+    int IN, S, head, T, NI;  // head = Fu + Fc + NI
+};
+__device__ __forceinline__ const float* dt_src(const DtSrc& s, int32_t cid) {
+    const int b = cid / s.S, slot = cid % s.S;
+    return slot < s.head ? s.dx0 + (int64_t)b * s.IN + slot * 32
+                         : s.dk + ((int64_t)b * s.T * s.NI + (slot - s.head)) * 32;
+}
+
+// One 32-lane group per sorted position that starts a piece (every DT_PIECE-th
+// position of its segment): the piece's sum in ascending contribution order.
+// A segment of one piece is finished here; otherwise the piece goes to
+// part[2 tile + (segment starts inside the tile)], tile = position / DT_PIECE
+// (a tile holds at most one piece start of a segment that began before it and
+// one of a longer-than-a-piece segment that begins in it).
+__global__ __launch_bounds__(256) void dt_emb_piece_kernel(const int32_t* __restrict__ cid,
+                                                           const int32_t* __restrict__ seg,
+                                                           const int32_t* __restrict__ starts, int64_t n, DtSrc src,
+                                                           float* __restrict__ vals, double* __restrict__ part) {
+    const int d = threadIdx.x & 31;
+    for (int64_t i = blockIdx.x * (int64_t)8 + (threadIdx.x >> 5); i < n; i += (int64_t)gridDim.x * 8) {
+        const int s = seg[i] - 1, st = starts[s];
+        if (((int)i - st) % DT_PIECE) continue;
+        const int en = starts[s + 1], e = min(en, (int)i + DT_PIECE);
+        double acc = 0.0;
+#pragma unroll 8  // eight (id, value) load pairs in flight: the chain is latency otherwise
+        for (int j = (int)i; j < e; ++j) acc += (double)dt_src(src, cid[j])[d];
+        if (en - st <= DT_PIECE) {
+            vals[(int64_t)s * 32 + d] = (float)acc;
+        } else {
+            const int tile = (int)i / DT_PIECE;
+            part[((int64_t)2 * tile + (st >= tile * DT_PIECE ? 1 : 0)) * 32 + d] = acc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dt_emb_long_kernel(const int32_t* __restrict__ starts,
+                                                          const int32_t* __restrict__ count,
+                                                          const double* __restrict__ part, float* __restrict__ vals) {
+    const int d = threadIdx.x & 31, n = *count;
+    for (int s = blockIdx.x * 8 + (threadIdx.x >> 5); s < n; s += gridDim.x * 8) {
+        const int st = starts[s], en = starts[s + 1];
+        if (en - st <= DT_PIECE) continue;
+        double acc = 0.0;
+        for (int i = st; i < en; i += DT_PIECE) {
+            const int tile = i / DT_PIECE;
+            acc += part[((int64_t)2 * tile + (st >= tile * DT_PIECE ? 1 : 0)) * 32 + d];
+        }
+        vals[(int64_t)s * 32 + d] = (float)acc;
+    }
+}
+
+// ------------------------------------------------------------------- Adam --
+// torch/optim/adam.py _single_tensor_adam, as tt_adam_kernel (tower_train.hip)
+struct DtAdamK {
+    float w1, beta2, w2, bc2_sqrt, eps, neg_step;
+};
+__device__ __forceinline__ void dt_adam(float& p, float& m, float& v, float g, const DtAdamK& k) {
+#pragma clang fp contract(off)
+    m = __fmaf_rn(k.w1, g - m, m);
+    v = __fmaf_rn(k.w2 * g, g, v * k.beta2);
+    const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
+    p = p + (k.neg_step * m) / denom;
+}
+
+// Blocks [0, wblocks): the packed weights, dense g.  Then the table, one
+// float4 per thread; a row's gradient by binary search in the compact list
+// (absent: g = 0; with m = v = 0 as well the row is left untouched).
+__global__ __launch_bounds__(256) void dt_adam_kernel(float* __restrict__ w, float* __restrict__ w_m,
+                                                      float* __restrict__ w_v, const float* __restrict__ w_g,
+                                                      int64_t n_w, int wblocks, float* __restrict__ tp,
+                                                      float* __restrict__ tm, float* __restrict__ tv,
+                                                      int64_t n_rows, const int32_t* __restrict__ rows,
+                                                      const float* __restrict__ vals,
+                                                      const int32_t* __restrict__ count, DtAdamK k) {
+    int64_t blk = blockIdx.x;
+    if (blk < wblocks) {
+        const int64_t e = blk * 256 + threadIdx.x;
+        if (e < n_w) {
+            float p = w[e], m = w_m[e], v = w_v[e];
+            dt_adam(p, m, v, w_g[e], k);
+            w[e] = p;
+            w_m[e] = m;
+            w_v[e] = v;
+        }
+        return;
+    }
+    blk -= wblocks;
+    const int64_t e4 = blk * 256 + threadIdx.x;  // float4 index, 8 per row
+    const int64_t row = e4 >> 3;
+    if (row >= n_rows) return;
+    int lo = 0, hi = *count;
+    const int n = hi;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rows[mid] < row) lo = mid + 1;
+        else hi = mid;
+    }
+    const bool has = lo < n && rows[lo] == row;
+    float4 m = reinterpret_cast<float4*>(tm)[e4], v = reinterpret_cast<float4*>(tv)[e4];
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (has) g = reinterpret_cast<const float4*>(vals)[(int64_t)lo * 8 + (e4 & 7)];
+    else if (m.x == 0.0f && m.y == 0.0f && m.z == 0.0f && m.w == 0.0f && v.x == 0.0f && v.y == 0.0f &&
+             v.z == 0.0f && v.w == 0.0f)
+        return;
+    float4 p = reinterpret_cast<float4*>(tp)[e4];
+    dt_adam(p.x, m.x, v.x, g.x, k);
+    dt_adam(p.y, m.y, v.y, g.y, k);
+    dt_adam(p.z, m.z, v.z, g.z, k);
+    dt_adam(p.w, m.w, v.w, g.w, k);
+    reinterpret_cast<float4*>(tp)[e4] = p;
+    reinterpret_cast<float4*>(tm)[e4] = m;
+    reinterpret_cast<float4*>(tv)[e4] = v;
+}
+
+// ------------------------------------------------------------------- host --
+static inline size_t dt_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct DtShape {
+    int Fu, NI, Fc, H1, H2, B, T, Di, IN, S;
+    int64_t R, N;
+};
+
+// packed weights: att_w0 [36, 4 Di] | att_b0 [36] | att_w1 [36] | att_b1 [1] |
+// mlp_w0 [H1, IN] | mlp_b0 [H1] | mlp_w1 [H2, H1] | mlp_b1 [H2] | mlp_w2 [H2] | mlp_b2 [1]
+struct DtOff {
+    int64_t aw0, ab0, aw1, ab1, w0, b0, w1, b1, w2, b2, n;
+};
+static DtOff dt_offsets(const DtShape& s) {
+    DtOff o{};
+    int64_t p = 0;
+    auto take = [&](int64_t n) {
+        const int64_t r = p;
+        p += n;
+        return r;
+    };
+    o.aw0 = take((int64_t)36 * 4 * s.Di);
+    o.ab0 = take(36);
+    o.aw1 = take(36);
+    o.ab1 = take(1);
+    o.w0 = take((int64_t)s.H1 * s.IN);
+    o.b0 = take(s.H1);
+    o.w1 = take((int64_t)s.H2 * s.H1);
+    o.b1 = take(s.H2);
+    o.w2 = take(s.H2);
+    o.b2 = take(1);
+    o.n = p;
+    return o;
+}
+
+static int dt_check(const char* fn, int64_t n_rows, int dim, int table_dtype, int n_user, int n_item, int n_ctx,
+                    int h1, int h2, int activation, int64_t batch, int seq_len, DtShape* s) {
+    auto fail = [&](int rc, const char* msg) {
+        set_error(std::string(fn) + ": " + msg);
+        return rc;
+    };
+    if (dim != DIN_E) return fail(NRK_EUNSUPPORTED, "training is built for din_embedding_dim == 32");
+    if (table_dtype != 0) return fail(NRK_EUNSUPPORTED, "training needs fp32 tables");
+    if (activation != 0) return fail(NRK_EUNSUPPORTED, "training implements the Dice activation only");
+    if (!(n_item == 1 || n_item == 2 || n_item == 4 || n_item == 8))
+        return fail(NRK_EUNSUPPORTED, "n_item must be 1, 2, 4 or 8");
+    if (n_user < 1 || n_user > DT_MAXF || n_ctx < 0 || n_ctx > DT_MAXF)
+        return fail(NRK_EUNSUPPORTED, "n_user must be in [1, 64] and n_ctx in [0, 64]");
+    if (h1 < 1 || h1 > DT_MAXH || h2 < 1 || h2 > DT_MAXH)
+        return fail(NRK_EUNSUPPORTED, "MLP hidden widths must be in [1, 1024]");
+    if (batch < 2 || batch > DT_MAXB)
+        return fail(NRK_EUNSUPPORTED, "batch must be in [2, 8192] (Dice uses the batch std)");
+    if (seq_len < 1 || seq_len > DT_MAXT) return fail(NRK_EUNSUPPORTED, "seq_len must be in [1, 128]");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX / 32) return fail(NRK_EINVAL, "bad n_table_rows");
+    s->Fu = n_user;
+    s->NI = n_item;
+    s->Fc = n_ctx;
+    s->H1 = h1;
+    s->H2 = h2;
+    s->B = (int)batch;
+    s->T = seq_len;
+    s->Di = n_item * 32;
+    s->IN = 32 * (n_user + n_ctx + 2 * n_item);
+    s->S = n_user + n_ctx + n_item + seq_len * n_item;
+    s->R = n_rows;
+    s->N = batch * s->S;
+    return NRK_OK;
+}
+
+struct DtWs {
+    float *z, *wbuf, *ds, *dsT, *Abuf, *Gq, *x0, *dx0, *z1, *a1, *da1, *z2, *da2, *hb, *loss_b, *dk;
+    double *gpart, *gemm_part, *epart;  // partial sums that a later kernel adds in order
+    double *mu_a, *sd_a, *S_a, *mu1, *sd1, *S1, *mu2, *sd2, *S2;  // Dice statistics and backward sums
+    uint32_t *keys, *keys2;
+    int32_t *cid, *cid2, *flag, *seg, *starts;
+    void* sort_tmp;
+    size_t sort_tmp_bytes, bytes;
+    int nblk, ksplit;
+};
+
+// upper bound of rocprim's temporary storage for the sort and the scan over n
+// pairs (queried exactly when a device is present, dt_sort_tmp_bytes)
+static size_t dt_sort_tmp_bound(int64_t n) { return (size_t)n * 16 + ((size_t)8 << 20); }
+
+static int dt_sort_bits(int64_t R) {
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < R) ++bits;
+    return bits;
+}
+
+static DtWs dt_layout(void* base, const DtShape& s) {
+    DtWs w{};
+    char* p = static_cast<char*>(base);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* r = p ? p + o : nullptr;
+        o += dt_al(bytes);
+        return r;
+    };
+    const size_t f = sizeof(float), B = s.B, C = (size_t)s.T * 36;
+    w.nblk = (s.B + DT_CB - 1) / DT_CB;
+    w.ksplit = std::max(1, std::min(16, s.B / 256));
+    w.z = (float*)take(f * B * C);
+    w.mu_a = (double*)take(8 * C);
+    w.sd_a = (double*)take(8 * C);
+    w.S_a = (double*)take(8 * 3 * C);
+    w.wbuf = (float*)take(f * B * s.T);
+    w.ds = (float*)take(f * B * s.T);
+    w.dsT = (float*)take(f * s.T);
+    w.Abuf = (float*)take(f * B * 36);
+    w.Gq = (float*)take(f * 36 * s.Di);
+    w.gpart = (double*)take(8 * (size_t)w.nblk * 2 * 36 * s.Di);
+    w.x0 = (float*)take(f * B * s.IN);
+    w.dx0 = (float*)take(f * B * s.IN);
+    w.z1 = (float*)take(f * B * s.H1);
+    w.mu1 = (double*)take(8 * (size_t)s.H1);
+    w.sd1 = (double*)take(8 * (size_t)s.H1);
+    w.a1 = (float*)take(f * B * s.H1);
+    w.da1 = (float*)take(f * B * s.H1);
+    w.S1 = (double*)take(8 * 3 * (size_t)s.H1);
+    w.z2 = (float*)take(f * B * s.H2);
+    w.mu2 = (double*)take(8 * (size_t)s.H2);
+    w.sd2 = (double*)take(8 * (size_t)s.H2);
+    w.da2 = (float*)take(f * B * s.H2);
+    w.S2 = (double*)take(8 * 3 * (size_t)s.H2);
+    w.hb = (float*)take(f * B * (s.H2 + 1));
+    w.loss_b = (float*)take(f * B);
+    w.gemm_part = (double*)take(8 * (size_t)w.ksplit * std::max({s.H1, s.H2, 36}) * std::max(s.IN, s.H1));
+    w.dk = (float*)take(f * B * s.T * s.Di);
+    w.epart = (double*)take(8 * 2 * 32 * (size_t)((s.N + DT_PIECE - 1) / DT_PIECE));
+    w.keys = (uint32_t*)take(4 * (size_t)s.N);
+    w.keys2 = (uint32_t*)take(4 * (size_t)s.N);
+    w.cid = (int32_t*)take(4 * (size_t)s.N);
+    w.cid2 = (int32_t*)take(4 * (size_t)s.N);
+    w.flag = (int32_t*)take(4 * (size_t)s.N);
+    w.seg = (int32_t*)take(4 * (size_t)s.N);
+    w.starts = (int32_t*)take(4 * (size_t)(s.N + 1));
+    w.sort_tmp_bytes = dt_sort_tmp_bound(s.N);
+    w.sort_tmp = take(w.sort_tmp_bytes);
+    w.bytes = o;
+    return w;
+}
+
+static int dt_gemm(hipStream_t st, const float* A, int64_t sam, int64_t sak, const float* Bm, int64_t sbk, int64_t sbn,
+                   const float* bias, float* C, int ldc, int M, int N, int K, int split, double* part) {
+    DtGemm g{A, Bm, bias, C, part, sam, sak, sbk, sbn, M, N, K, ldc, 0};
+    split = std::max(1, std::min(split, (K + 15) / 16));
+    g.kper = ((K + split - 1) / split + 15) / 16 * 16;
+    split = (K + g.kper - 1) / g.kper;
+    dt_gemm_kernel<<<dim3((N + 63) / 64, (M + 63) / 64, split), 256, 0, st>>>(g);
+    if (split > 1) dt_sum_parts_kernel<<<(M * N + 255) / 256, 256, 0, st>>>(part, split, M, N, ldc, C);
+    return hipGetLastError() == hipSuccess ? NRK_OK : NRK_EHIP;
+}
+
+template <int NI>
+static int dt_run(const DtShape& s, const DtWs& w, const DtIdx& ix, const float* wts, const float* labels, float* loss,
+                  float* wg, int32_t* rows, float* vals, int32_t* count, hipStream_t st) {
+    const DtOff o = dt_offsets(s);
+    const int B = s.B, T = s.T, Di = s.Di, IN = s.IN, H1 = s.H1, H2 = s.H2, C = T * 36, WS = Di + 1;
+    const int ew = 2048;  // blocks of the grid-stride elementwise kernels
+    auto eg = [&](int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, ew); };
+    // ---- forward
+    const size_t lds_fwd = sizeof(float) * (36 * WS + Di + 36) + sizeof(int) * T * NI;
+    dt_att_fwd_kernel<NI><<<B, 256, lds_fwd, st>>>(ix, wts + o.aw0, wts + o.ab0, w.z);
+    dt_colstat_kernel<<<(C + 15) / 16, 1024, 0, st>>>(w.z, B, C, w.mu_a, w.sd_a);
+    const size_t lds_out = sizeof(float) * (T * 36 + T + Di) + sizeof(int) * T * NI;
+    dt_att_out_kernel<NI><<<B, 256, lds_out, st>>>(ix, w.z, w.mu_a, w.sd_a, wts + o.aw1, wts + o.ab1, IN, w.wbuf, w.x0);
+    NRK_CHECK_LAUNCH();
+    if (dt_gemm(st, w.x0, IN, 1, wts + o.w0, 1, IN, wts + o.b0, w.z1, H1, B, H1, IN, 1, nullptr)) return NRK_EHIP;
+    dt_colstat_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.z1, B, H1, w.mu1, w.sd1);
+    dt_dice_fwd_kernel<<<eg((int64_t)B * H1), 256, 0, st>>>(w.z1, w.mu1, w.sd1, (int64_t)B * H1, H1, w.a1);
+    if (dt_gemm(st, w.a1, H1, 1, wts + o.w1, 1, H1, wts + o.b1, w.z2, H2, B, H2, H1, 1, nullptr)) return NRK_EHIP;
+    dt_colstat_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.z2, B, H2, w.mu2, w.sd2);
+    dt_head_kernel<<<(B + 3) / 4, 256, 0, st>>>(w.z2, w.mu2, w.sd2, wts + o.w2, wts + o.b2, labels, B, H2, w.loss_b,
+                                                w.hb, w.da2);
+    dt_loss_kernel<<<1, 1024, 0, st>>>(w.loss_b, B, loss);
+    NRK_CHECK_LAUNCH();
+    // ---- backward: MLP
+    dt_colsum_kernel<<<(H2 + 1 + 15) / 16, 1024, 0, st>>>(w.hb, B, H2 + 1, wg + o.w2);  // d w2 | d b2
+    dt_dice_sums_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.z2, w.mu2, w.sd2, w.da2, H2, 1, nullptr, B, H2, w.S2);
+    dt_dice_bwd_kernel<<<eg((int64_t)B * H2), 256, 0, st>>>(w.z2, w.mu2, w.sd2, w.S2, B, H2, w.da2);  // da2 := dz2
+    dt_colsum_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.da2, B, H2, wg + o.b1);
+    if (dt_gemm(st, w.da2, 1, H2, w.a1, H1, 1, nullptr, wg + o.w1, H1, H2, H1, B, w.ksplit, w.gemm_part))
+        return NRK_EHIP;
+    if (dt_gemm(st, w.da2, H2, 1, wts + o.w1, H1, 1, nullptr, w.da1, H1, B, H1, H2, 1, nullptr)) return NRK_EHIP;
+    dt_dice_sums_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.z1, w.mu1, w.sd1, w.da1, H1, 1, nullptr, B, H1, w.S1);
+    dt_dice_bwd_kernel<<<eg((int64_t)B * H1), 256, 0, st>>>(w.z1, w.mu1, w.sd1, w.S1, B, H1, w.da1);  // da1 := dz1
+    dt_colsum_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.da1, B, H1, wg + o.b0);
+    if (dt_gemm(st, w.da1, 1, H1, w.x0, IN, 1, nullptr, wg + o.w0, IN, H1, IN, B, w.ksplit, w.gemm_part))
+        return NRK_EHIP;
+    if (dt_gemm(st, w.da1, H1, 1, wts + o.w0, IN, 1, nullptr, w.dx0, IN, B, IN, H1, 1, nullptr)) return NRK_EHIP;
+    NRK_CHECK_LAUNCH();
+    // ---- backward: attention
+    dt_att_ds_kernel<NI><<<B, 256, 0, st>>>(ix, w.dx0, IN, w.ds);
+    dt_colsum_kernel<<<(T + 15) / 16, 1024, 0, st>>>(w.ds, B, T, w.dsT);
+    dt_dice_sums_kernel<<<(C + 15) / 16, 1024, 0, st>>>(w.z, w.mu_a, w.sd_a, w.ds, T, 36, wts + o.aw1, B, C, w.S_a);
+    const size_t lds_bwd = sizeof(float) * (36 * WS + 2 * Di + 256 + 40 + T + T * 36) + sizeof(int) * T * NI;
+    dt_att_bwd_kernel<NI><<<w.nblk, 256, lds_bwd, st>>>(ix, wts + o.aw0, wts + o.aw1, w.mu_a, w.sd_a, w.S_a, w.ds,
+                                                        w.wbuf, IN, w.z, w.dx0, w.dk, w.Abuf, w.gpart);
+    NRK_CHECK_LAUNCH();
+    dt_colsum_kernel<<<(36 + 15) / 16, 1024, 0, st>>>(w.Abuf, B, 36, wg + o.ab0);
+    if (dt_gemm(st, w.Abuf, 1, 36, w.x0 + (s.Fu + s.Fc) * 32, IN, 1, nullptr, w.Gq, Di, 36, Di, B, w.ksplit,
+                w.gemm_part))
+        return NRK_EHIP;
+    dt_att_final_kernel<<<(36 * Di + 37 + 255) / 256, 256, 0, st>>>(w.gpart, w.nblk, Di, w.Gq, w.S_a + 2 * C, w.dsT,
+                                                                     T, wg + o.aw0, wg + o.aw1, wg + o.ab1);
+    NRK_CHECK_LAUNCH();
+    // ---- embedding gradients
+    const int64_t N = s.N;
+    dt_emb_keys_kernel<<<eg(N), 256, 0, st>>>(ix, NI, N, w.keys, w.cid);
+    NRK_CHECK_LAUNCH();
+    size_t need = 0;
+    const int bits = dt_sort_bits(s.R);
+    if (rocprim::radix_sort_pairs(nullptr, need, w.keys, w.keys2, w.cid, w.cid2, (size_t)N, 0u, (unsigned)bits, st) !=
+            hipSuccess ||
+        need > w.sort_tmp_bytes) {
+        set_error("nrk_din_train_grad: radix sort temporary storage exceeds the workspace bound");
+        return NRK_EHIP;
+    }
+    need = w.sort_tmp_bytes;
+    if (rocprim::radix_sort_pairs(w.sort_tmp, need, w.keys, w.keys2, w.cid, w.cid2, (size_t)N, 0u, (unsigned)bits,
+                                  st) != hipSuccess) {
+        set_error("nrk_din_train_grad: radix sort failed");
+        return NRK_EHIP;
+    }
+    dt_emb_heads_kernel<<<eg(N), 256, 0, st>>>(w.keys2, N, w.flag);
+    need = 0;
+    if (rocprim::inclusive_scan(nullptr, need, w.flag, w.seg, (size_t)N, rocprim::plus<int32_t>(), st) != hipSuccess ||
+        need > w.sort_tmp_bytes) {
+        set_error("nrk_din_train_grad: scan temporary storage exceeds the workspace bound");
+        return NRK_EHIP;
+    }
+    need = w.sort_tmp_bytes;
+    if (rocprim::inclusive_scan(w.sort_tmp, need, w.flag, w.seg, (size_t)N, rocprim::plus<int32_t>(), st) !=
+        hipSuccess) {
+        set_error("nrk_din_train_grad: scan failed");
+        return NRK_EHIP;
+    }
+    dt_emb_starts_kernel<<<eg(N), 256, 0, st>>>(w.keys2, w.flag, w.seg, N, w.starts, rows, count);
+    DtSrc src{w.dx0, w.dk, IN, s.S, s.Fu + s.Fc + NI, T, NI};
+    const int pg = (int)std::min<int64_t>((N + 7) / 8, 8192);
+    dt_emb_piece_kernel<<<pg, 256, 0, st>>>(w.cid2, w.seg, w.starts, N, src, vals, w.epart);
+    dt_emb_long_kernel<<<pg, 256, 0, st>>>(w.starts, count, w.epart, vals);
+    NRK_CHECK_LAUNCH();
+    return NRK_OK;
+}
+
+}  // namespace nrk
+
+using namespace nrk;
+
+extern "C" {
+
+size_t nrk_din_train_workspace_bytes(int64_t n_table_rows, int dim, int table_dtype, int n_user, int n_item,
+                                     int n_ctx, int h1, int h2, int activation, int64_t batch, int seq_len) {
+    clear_error();
+    DtShape s{};
+    if (dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, h1, h2, activation, batch, seq_len,
+                 &s) != NRK_OK)
+        return 0;
+    return dt_layout(nullptr, s).bytes;
+}
+
+int nrk_din_train_grad(const float* table, int64_t n_table_rows, int dim, int table_dtype, const int64_t* row_base,
+                       int n_user, int n_item, int n_ctx, const float* weights, int h1, int h2, int activation,
+                       const int32_t* user_idx, const int32_t* item_idx, const int32_t* hist_idx,
+                       const int32_t* ctx_idx, const float* mask, const float* labels, int64_t batch, int seq_len,
+                       float* loss, float* w_grad, int32_t* t_rows, float* t_vals, int32_t* t_count, void* workspace,
+                       size_t workspace_bytes, nrk_stream_t stream) {
+    clear_error();
+    DtShape s{};
+    const int rc = dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, h1, h2, activation, batch,
+                            seq_len, &s);
+    if (rc != NRK_OK) return rc;
+    NRK_REQUIRE(table && row_base && weights && user_idx && item_idx && hist_idx && (ctx_idx || n_ctx == 0) && mask &&
+                    labels && loss && w_grad && t_rows && t_vals && t_count && workspace,
+                "null pointer");
+    const DtWs w = dt_layout(workspace, s);
+    NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small (nrk_din_train_workspace_bytes)");
+    const DtIdx ix{table, row_base, user_idx, item_idx, hist_idx, ctx_idx, mask, n_user, n_ctx, s.B, s.T};
+    hipStream_t st = as_stream(stream);
+    switch (n_item) {
+        case 1: return dt_run<1>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        case 2: return dt_run<2>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        case 4: return dt_run<4>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        default: return dt_run<8>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+    }
+}
+
+int nrk_din_adam_step(float* weights, float* w_m, float* w_v, const float* w_grad, int64_t n_weights, float* table,
+                      float* t_m, float* t_v, int64_t n_table_rows, int dim, const int32_t* t_rows,
+                      const float* t_vals, const int32_t* t_count, double lr, double beta1, double beta2, double eps,
+                      int64_t t, nrk_stream_t stream) {
+    clear_error();
+    if (dim != DIN_E) NRK_UNSUPPORTED("training is built for din_embedding_dim == 32");
+    NRK_REQUIRE(n_weights > 0 && n_weights < ((int64_t)1 << 31), "bad n_weights");
+    NRK_REQUIRE(n_table_rows > 0 && n_table_rows <= (int64_t)INT32_MAX / 32, "bad n_table_rows");
+    NRK_REQUIRE(t >= 1, "t is the 1-based step number");
+    NRK_REQUIRE(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+                "bad hyper-parameters");
+    NRK_REQUIRE(weights && w_m && w_v && w_grad && table && t_m && t_v && t_rows && t_vals && t_count, "null pointer");
+    // the scalars as _single_tensor_adam forms them, in double, then one rounding to fp32
+    const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
+    const DtAdamK k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)std::sqrt(bc2), (float)eps,
+                    (float)(-(lr / bc1))};
+    const int wblocks = (int)((n_weights + 255) / 256);
+    const int64_t tblocks = (n_table_rows * 8 + 255) / 256;
+    dt_adam_kernel<<<(unsigned)(wblocks + tblocks), 256, 0, as_stream(stream)>>>(
+        weights, w_m, w_v, w_grad, n_weights, wblocks, table, t_m, t_v, n_table_rows, t_rows, t_vals, t_count, k);
+    NRK_CHECK_LAUNCH();
+    return NRK_OK;
+}
+
+}  // extern "C"

@@ -761,6 +761,185 @@ def din_workspace(p: DinParams, B, T, device, batch_size=None):
     return torch.empty(nb, dtype=torch.uint8, device=device)
 
 
+# ----------------------------------------------------------- DIN training --
+DIN_GROUPS = ("user_profile_embedding_dict", "item_embedding_dict", "context_embedding_dict")
+
+
+def din_state_keys(user_feats, item_feats, ctx_feats):
+    """(table keys, packed-weight keys, alpha keys, DINModel.state_dict() key
+    order) of a two-hidden-layer Dice DINModel (DIN.py:133-212)."""
+    tabs = [f"{g}.{f}.weight" for g, fs in zip(DIN_GROUPS, (user_feats, item_feats, ctx_feats)) for f in fs]
+    wts = ["activation_unit.mlp.0.weight", "activation_unit.mlp.0.bias", "activation_unit.mlp.2.weight",
+           "activation_unit.mlp.2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias",
+           "mlp.4.weight", "mlp.4.bias"]
+    alphas = ["activation_unit.mlp.1.alpha", "mlp.1.alpha", "mlp.3.alpha"]
+    order = tabs + wts[:2] + alphas[:1] + wts[2:6] + alphas[1:2] + wts[6:8] + alphas[2:] + wts[8:]
+    return tabs, wts, alphas, order
+
+
+class DinTrainParams:
+    """A DINModel's parameters with their Adam moments on the device in the
+    layout of nrk_din_train_grad: the per-feature embedding tables
+    concatenated row-wise (``row_base`` as DinParams), the Linear layers as one
+    packed vector, the Dice alphas (no gradient, never updated) as given.
+    Shapes outside the compiled training variants (din_embedding_dim != 32,
+    item-feature counts other than 1, 2, 4, 8, bf16 tables, ...) raise
+    NotImplementedError: they stay inference-only."""
+
+    def __init__(self, state_dict, user_feats, item_feats, ctx_feats, table_dtype="fp32", device="cuda"):
+        import numpy as np
+
+        def arr(k):
+            v = state_dict[k]
+            v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+            return np.ascontiguousarray(v, dtype=np.float32)
+
+        self.feats = (list(user_feats), list(item_feats), list(ctx_feats))
+        self.tab_keys, self.w_keys, self.alpha_keys, self.order = din_state_keys(*self.feats)
+        if table_dtype not in ("fp32", "bf16"):
+            raise ValueError("table_dtype must be 'fp32' or 'bf16'")
+        self.table_code = 0 if table_dtype == "fp32" else 1
+        tabs = [arr(k) for k in self.tab_keys]
+        if not self.feats[0] or not self.feats[1]:
+            raise ValueError("DIN needs at least one user and one item feature")
+        self.dim = int(tabs[0].shape[1])
+        if any(t.ndim != 2 or t.shape[1] != self.dim for t in tabs):
+            raise ValueError("every embedding table must have the same width (din_embedding_dim)")
+        self.n_user, self.n_item, self.n_ctx = (len(f) for f in self.feats)
+        self.vocab = [int(t.shape[0]) for t in tabs]
+        self.n_rows = sum(self.vocab)
+        ws = [arr(k) for k in self.w_keys]
+        self.w_shapes = [w.shape for w in ws]
+        self.h1, self.h2 = int(ws[4].shape[0]), int(ws[6].shape[0])
+        self.workspace_bytes(2, 1)  # refuses what the kernels are not built for
+        n_in = self.dim * (self.n_user + self.n_ctx + 2 * self.n_item)
+        exp = [(36, 4 * self.n_item * self.dim), (36,), (1, 36), (1,), (self.h1, n_in), (self.h1,),
+               (self.h2, self.h1), (self.h2,), (1, self.h2), (1,)]
+        if [tuple(s) for s in self.w_shapes] != exp:
+            raise ValueError("state_dict shapes do not match the feature lists")
+        self.device = torch.device(device)
+        self.table = torch.from_numpy(np.concatenate(tabs, 0)).to(self.device).contiguous()
+        self.row_base = torch.from_numpy(np.cumsum([0] + self.vocab[:-1]).astype(np.int64)).to(self.device)
+        self.weights = torch.from_numpy(np.concatenate([w.reshape(-1) for w in ws])).to(self.device).contiguous()
+        # as given, shape included (0-d in the reference): no gradient, never updated
+        self.alphas = {k: torch.as_tensor(np.array(arr(k), np.float32).reshape(np.shape(state_dict[k]))).clone()
+                       for k in self.alpha_keys}
+        self.t_m, self.t_v = torch.zeros_like(self.table), torch.zeros_like(self.table)
+        self.w_m, self.w_v = torch.zeros_like(self.weights), torch.zeros_like(self.weights)
+        self.t = 0  # Adam steps taken
+
+    def workspace_bytes(self, batch, seq_len):
+        L = _lib.lib()
+        nb = L.nrk_din_train_workspace_bytes(self.n_rows, self.dim, self.table_code, self.n_user, self.n_item,
+                                             self.n_ctx, self.h1, self.h2, 0, batch, seq_len)
+        if not nb:
+            raise NotImplementedError("nrk_din_train_workspace_bytes: " + L.nrk_last_error().decode(errors="replace"))
+        return nb
+
+    def split_weights(self, packed):
+        """Packed vector -> {state_dict key: view of its shape}."""
+        out, off = {}, 0
+        for k, s in zip(self.w_keys, self.w_shapes):
+            n = 1
+            for x in s:
+                n *= int(x)
+            out[k] = packed[off:off + n].view(*s)
+            off += n
+        return out
+
+    def split_table(self, table):
+        out, off = {}, 0
+        for k, v in zip(self.tab_keys, self.vocab):
+            out[k] = table[off:off + v]
+            off += v
+        return out
+
+    def state_dict(self):
+        """CPU tensors under DINModel.state_dict()'s keys, in its order."""
+        sd = {**self.split_table(self.table), **self.split_weights(self.weights)}
+        sd = {k: v.detach().cpu().clone() for k, v in sd.items()}
+        sd.update({k: v.clone() for k, v in self.alphas.items()})
+        return {k: sd[k] for k in self.order}
+
+
+class DinGrads:
+    """Outputs of din_train_grad.  ``loss`` [1]; ``w_grad`` dense over the
+    packed weights; the table's gradient as ``t_count`` [1] ascending unique
+    virtual rows ``t_rows`` with ``t_vals`` [rows, 32] (capacity: the batch's
+    contributions or the table, whichever is smaller)."""
+
+    def __init__(self, p: DinTrainParams, batch, seq_len):
+        f = dict(dtype=torch.float32, device=p.device)
+        self.batch, self.seq_len = batch, seq_len
+        cap = min(p.n_rows, batch * (p.n_user + p.n_ctx + p.n_item * (1 + seq_len)))
+        self.loss = torch.zeros(1, **f)
+        self.w_grad = torch.empty(p.weights.numel(), **f)
+        self.t_rows = torch.empty(cap, dtype=torch.int32, device=p.device)
+        self.t_vals = torch.empty((cap, 32), **f)
+        self.t_count = torch.zeros(1, dtype=torch.int32, device=p.device)
+
+    def table_grad(self):
+        n = int(self.t_count)
+        return self.t_rows[:n], self.t_vals[:n]
+
+    def dense(self, p: DinTrainParams):
+        """{state_dict key: dense gradient} of every trained parameter: the
+        compact list scattered back to per-feature [vocab, 32] tables."""
+        rows, vals = self.table_grad()
+        table = torch.zeros_like(p.table)
+        table[rows.long()] = vals
+        return {**p.split_table(table), **p.split_weights(self.w_grad)}
+
+
+def din_train_check(p: DinTrainParams, user, item, hist, ctx, labels):
+    """Range check of index tensors and labels (device syncs), once before the
+    first step: what din_train_grad's kernels trust."""
+    din_validate(p, user, item, hist, ctx)
+    if labels.numel() and not bool(((labels == 0) | (labels == 1)).all()):
+        raise ValueError("labels must be 0 or 1")
+
+
+def din_train_grad(p: DinTrainParams, user, item, hist, ctx, mask, labels, out=None, loss=None, validate=True):
+    """One DIN training batch without the optimiser (DIN.py:907-912): forward
+    in train mode, mean BCELoss, backward.  Index tensors and mask as
+    din_forward, ``labels`` [B] fp32 of 0 / 1.  ``out``: a DinGrads of the
+    same shapes to reuse; ``loss``: a fp32 [1] device tensor (e.g. a slice of
+    a per-step loss vector) to write instead of out.loss.  ``validate=False``
+    skips the range checks for a loop over data it checked once."""
+    _dev(user, item, hist, ctx, mask, labels, loss)
+    B, T = mask.shape
+    _need(user, torch.int32, (B, p.n_user), "user")
+    _need(item, torch.int32, (B, p.n_item), "item")
+    _need(hist, torch.int32, (B, T, p.n_item), "hist")
+    _need(ctx, torch.int32, (B, p.n_ctx), "ctx")
+    _need(mask, torch.float32, (B, T), "mask")
+    _need(labels, torch.float32, (B,), "labels")
+    if loss is not None:
+        _need(loss, torch.float32, (1,), "loss")
+    nbytes = p.workspace_bytes(B, T)
+    if validate:
+        din_train_check(p, user, item, hist, ctx, labels)
+    ws = _tt_ws(p.device, nbytes)
+    if out is None:
+        out = DinGrads(p, B, T)
+    elif (out.batch, out.seq_len) != (B, T):
+        raise ValueError("out: a DinGrads of another shape")
+    _lib.call("nrk_din_train_grad", _ptr(p.table), p.n_rows, p.dim, p.table_code, _ptr(p.row_base), p.n_user,
+              p.n_item, p.n_ctx, _ptr(p.weights), p.h1, p.h2, 0, _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx),
+              _ptr(mask), _ptr(labels), B, T, _ptr(out.loss if loss is None else loss), _ptr(out.w_grad),
+              _ptr(out.t_rows), _ptr(out.t_vals), _ptr(out.t_count), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def din_adam_step(p: DinTrainParams, grads: DinGrads, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+    """One torch.optim.Adam step (dense semantics) in place over the packed
+    weights and the whole table from din_train_grad's outputs."""
+    p.t += 1
+    _lib.call("nrk_din_adam_step", _ptr(p.weights), _ptr(p.w_m), _ptr(p.w_v), _ptr(grads.w_grad), p.weights.numel(),
+              _ptr(p.table), _ptr(p.t_m), _ptr(p.t_v), p.n_rows, p.dim, _ptr(grads.t_rows), _ptr(grads.t_vals),
+              _ptr(grads.t_count), float(lr), float(betas[0]), float(betas[1]), float(eps), p.t, _stream())
+
+
 # ----------------------------------------------------------------- itemcf --
 class ItemCFSim:
     """Device result of nrk_itemcf_sim: one entry per distinct (i, j), sorted

@@ -4,8 +4,8 @@
 reference's generic ``load`` reads train / test feature sets and history
 dicts from ``config.train_set_path`` etc. -- fields ``RankConfig`` does not
 define, so it raises there; ``DINRanker``
-overrides it (DIN.py:529-558), as the reference's does.  Training is out of
-scope for this hot path: ``train()`` stays the reference's no-op.
+overrides it (DIN.py:529-558), as the reference's does.  ``train()`` is the
+reference's no-op here; ``DINRanker`` overrides it.
 """
 from __future__ import annotations
 

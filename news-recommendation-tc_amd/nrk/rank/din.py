@@ -14,10 +14,14 @@
   to main_df.  Like the reference, Dice uses the statistics of each batch, so
   a batch is the unit of work; a trailing batch of one row is NaN there (std
   of one sample) and is NaN here too.
+* ``DINRanker.train`` / ``train_on_encoded`` / ``save_model`` train the model
+  on the device (ops.din_train_grad + ops.din_adam_step) and write the
+  reference's artifacts.
 """
 from __future__ import annotations
 
 import os
+import pickle
 from collections.abc import Mapping
 from typing import Optional
 
@@ -111,6 +115,35 @@ def _expected_state(uv, iv, cv, dim, mlp_hidden):
     return exp
 
 
+def _batched_bce(probs, labels, batch_size):
+    """Mean over the batches of nn.BCELoss per batch (DIN.py:946-965), and the
+    accuracy at 0.5 over all rows."""
+    p, y = np.asarray(probs, np.float64), np.asarray(labels, np.float64)
+    losses = []
+    for s in range(0, len(p), batch_size):
+        q, t = p[s:s + batch_size], y[s:s + batch_size]
+        with np.errstate(divide="ignore"):
+            losses.append(float(np.mean(-(t * np.maximum(np.log(q), -100) + (1 - t) * np.maximum(np.log1p(-q), -100)))))
+    return float(np.mean(losses)), float(np.mean((p > 0.5) == (y > 0.5)))
+
+
+def _validation_metrics(labels, probs):
+    """DIN.py:1065-1128: AUC, log loss, accuracy, precision, recall, F1 at 0.5."""
+    from sklearn import metrics as M
+
+    y, p = np.asarray(labels).astype(int), np.asarray(probs, np.float64)
+    ok = np.isfinite(p)
+    y, p = y[ok], p[ok]
+    pred = (p > 0.5).astype(int)
+    two = len(np.unique(y)) > 1
+    return {"auc_roc": float(M.roc_auc_score(y, p)) if two else float("nan"),
+            "log_loss": float(M.log_loss(y, np.clip(p, 1e-15, 1 - 1e-15), labels=[0, 1])),
+            "accuracy": float(M.accuracy_score(y, pred)),
+            "precision": float(M.precision_score(y, pred, zero_division=0)),
+            "recall": float(M.recall_score(y, pred, zero_division=0)),
+            "f1_score": float(M.f1_score(y, pred, zero_division=0))}
+
+
 class DINRanker(BaseRanker):
     """Ranker plugin: drop-in for src/rank/DIN.py's DINRanker on the serving
     path RankPipeline drives (rank_pipeline.py:96-141):
@@ -129,15 +162,18 @@ class DINRanker(BaseRanker):
       ``load_state_dict`` -- into device weights for the HIP kernels;
     * ``predict`` (:1219-1283): every main_df row in order, Dice batches of
       ``config.batch_size``.
+    * ``train`` (:703-1005) runs on the device: the fused step of
+      csrc/din_train.hip and its Adam sweep (``train_on_encoded`` is the
+      deterministic core), then ``save_model`` (:1285-1326).
     Alternate entry points for in-memory data: ``set_data(...)`` and
-    ``load_model(state_dict)``.  Training stays with the reference (out of
-    scope); ``train()`` is BaseRanker's no-op."""
+    ``load_model(state_dict)``."""
 
     def __init__(self, config: Optional[RankConfig] = None, device="cuda", table_dtype="fp32"):
         super().__init__(config or RankConfig())
         self.device = device
         self.table_dtype = table_dtype
         self.model = None  # DINScorer: the model's weights on the device
+        self.trainer = None  # ops.DinTrainParams: parameters and Adam moments while training
         self.label_encoders = {}
         self.encoder = None
         self._tables = None
@@ -244,9 +280,223 @@ class DINRanker(BaseRanker):
         self.encoder, self._tables = None, None
         return self
 
+    # ----------------------------------------------------------- train --
+    def _apply_negative_sampling(self, df, ratio=None, dataset_name="Dataset"):
+        """DIN.py:621-701 with the same pandas calls and ``random_seed``: all
+        positives, ``int(n_pos * ratio)`` sampled negatives, concatenated and
+        shuffled (host ETL; row for row the reference's frame)."""
+        import pandas as pd
+
+        if "label" not in df.columns:
+            return df
+        pos, neg = df[df["label"] == 1], df[df["label"] == 0]
+        ratio = ratio if ratio is not None else self.config.negative_positive_ratio
+        if len(pos) == 0:
+            return df
+        target = int(len(pos) * ratio)
+        if target >= len(neg):
+            return df
+        seed = self.config.random_seed
+        np.random.seed(seed)
+        sampled = neg.sample(n=target, random_state=seed)
+        balanced = pd.concat([pos, sampled], ignore_index=True)
+        return balanced.sample(frac=1, random_state=seed).reset_index(drop=True)
+
+    def _init_state(self, uv, iv, cv):
+        """DINModel's initial state_dict (DIN.py:133-212) under
+        ``torch.manual_seed(config.random_seed)``: throw-away CPU modules of
+        the model's shapes built in the model's construction order (the
+        nn.Embedding tables of the three groups, the ActivationUnit's two
+        nn.Linear, the MLP's nn.Linear), so the generator is consumed exactly as
+        ``DINModel(...)`` consumes it; a Dice ``alpha`` holds its layer's width,
+        as the reference's ``Dice(unit)`` leaves it (unused, never trained)."""
+        import torch.nn as nn
+
+        dim, hidden = self.config.din_embedding_dim, list(self.config.din_mlp_hidden_units)
+        torch.manual_seed(self.config.random_seed)
+        sd = {}
+        for grp, vocab in (("user_profile_embedding_dict", uv), ("item_embedding_dict", iv),
+                           ("context_embedding_dict", cv)):
+            for f, v in vocab.items():
+                sd[f"{grp}.{f}.weight"] = nn.Embedding(v, dim).weight.detach()
+        item_dim = len(iv) * dim
+        units = [("activation_unit.mlp.0", 4 * item_dim, 36), ("activation_unit.mlp.2", 36, 1)]
+        cur = (len(uv) + len(cv)) * dim + 2 * item_dim
+        for n, unit in enumerate(hidden):
+            units.append((f"mlp.{2 * n}", cur, unit))
+            cur = unit
+        units.append((f"mlp.{2 * len(hidden)}", cur, 1))
+        for name, fan_in, out in units:
+            lin = nn.Linear(fan_in, out)
+            sd[name + ".weight"], sd[name + ".bias"] = lin.weight.detach(), lin.bias.detach()
+        # Dice(unit) hands the layer width to ``alpha`` (DIN.py:72, :204): 36.0, then the MLP widths
+        sd["activation_unit.mlp.1.alpha"] = torch.tensor(36.0, dtype=torch.float32)
+        for n, unit in enumerate(hidden):
+            sd[f"mlp.{2 * n + 1}.alpha"] = torch.tensor(float(unit), dtype=torch.float32)
+        return {k: sd[k] for k in _expected_state(uv, iv, cv, dim, hidden)}
+
+    def train_on_encoded(self, enc, labels, batch_size, epochs, learning_rate, order=None, init_state=None):
+        """The deterministic core of ``train``: Adam over ``epochs`` passes of
+        the encoded samples (``DinEncoder.encode_device`` output, or host
+        arrays) in batches of ``batch_size``, the last one short
+        (``drop_last=False``); a trailing batch of one row is skipped with a
+        warning (its Dice std is NaN in the reference).  ``order``: an
+        explicit [epochs, n] permutation; by default a device
+        ``torch.randperm`` per epoch seeded with ``random_seed + epoch`` (a
+        uniform permutation, not the DataLoader's draws).  ``init_state``: a
+        DINModel state_dict to start from (default: continue the current
+        trainer).  Per-step losses stay on the device and are read once per
+        epoch: returns them as a CPU tensor and appends
+        ``(epoch_fraction, loss)`` to ``loss_history``."""
+        import warnings
+
+        dev = torch.device(self.device)
+        if init_state is not None or getattr(self, "trainer", None) is None:
+            if init_state is None:
+                raise ValueError("train_on_encoded needs init_state for the first call")
+            self.trainer = ops.DinTrainParams(init_state, self.user_profile_features, self.item_features,
+                                              self.context_features, table_dtype=self.table_dtype, device=dev)
+        p = self.trainer
+        t = lambda a, dt: torch.as_tensor(a).to(dev, dt).contiguous()  # noqa: E731
+        data = [t(enc["user"], torch.int32), t(enc["item"], torch.int32), t(enc["hist"], torch.int32),
+                t(enc["ctx"], torch.int32), t(enc["mask"], torch.float32), t(labels, torch.float32)]
+        n = data[0].shape[0]
+        ops.din_train_check(p, data[0], data[1], data[2], data[3], data[5])
+        bounds = [(s, min(n, s + batch_size)) for s in range(0, n, batch_size)]
+        if bounds and bounds[-1][1] - bounds[-1][0] == 1:
+            warnings.warn("DIN training: the trailing batch of one row is skipped (Dice's std of one sample is NaN)")
+            bounds.pop()
+        if not bounds:
+            raise ValueError("DIN training needs at least one batch of two rows")
+        if order is not None:
+            order = torch.as_tensor(order).to(dev, torch.int64).reshape(epochs, n)
+        if not hasattr(self, "loss_history"):
+            self.loss_history = []
+        grads = {}
+        all_losses = []
+        for epoch in range(epochs):
+            if order is not None:
+                perm = order[epoch]
+            else:
+                gen = torch.Generator(device=dev)
+                gen.manual_seed(int(self.config.random_seed) + epoch)
+                perm = torch.randperm(n, device=dev, generator=gen)
+            shuffled = [x.index_select(0, perm).contiguous() for x in data]
+            losses = torch.zeros(len(bounds), dtype=torch.float32, device=dev)
+            for i, (s, e) in enumerate(bounds):
+                g = grads.get(e - s)
+                g = grads[e - s] = ops.din_train_grad(p, *[x[s:e] for x in shuffled], out=g, loss=losses[i:i + 1],
+                                                     validate=False)
+                ops.din_adam_step(p, g, lr=learning_rate)
+            host = losses.cpu()  # the epoch's one read
+            all_losses.append(host)
+            self.loss_history += [(epoch + (i + 1) / len(bounds), float(v)) for i, v in enumerate(host)]
+        self.model = None  # the scorer of the previous weights is stale
+        return torch.cat(all_losses)
+
+    def state_dict(self):
+        """The trained parameters under DINModel.state_dict()'s keys and order."""
+        if getattr(self, "trainer", None) is None:
+            raise ValueError("No model to save. Train the model first.")
+        return self.trainer.state_dict()
+
+    def _scorer_from_trainer(self):
+        self.model = DINScorer(self.trainer.state_dict(), self.user_profile_features, self.item_features,
+                               self.context_features, table_dtype=self.table_dtype, device=self.device)
+        return self.model
+
+    def _encode_frame(self, df):
+        cols = iloc_columns(df, ["user_id", "item_id"] + list(self.context_features))
+        return self.encoder.encode_device(self._tables, cols["user_id"], cols["item_id"], cols)
+
+    def train(self):
+        """DIN.py:703-1005 without the plots and the JSON log: split on
+        ``is_train`` / ``is_val`` (80 / 20 of the rows without them), negative
+        sampling of both parts, ``_prepare_vocab_dicts``, the reference's
+        initialisation (``_init_state``), ``config.epochs`` epochs of
+        ``train_on_encoded``, after each the validation loss and accuracy
+        from the inference kernels in Dice batches of ``batch_size``
+        (``val_loss_history``), the final validation metrics
+        (``final_metrics``), then ``label_encoders.pkl`` and ``save_model``."""
+        cfg = self.config
+        if getattr(self, "main_df", None) is None:
+            self.load()
+        df = self.main_df
+        if "is_train" in df.columns and "is_val" in df.columns:
+            train_data, val_data = df[df["is_train"] == True].copy(), df[df["is_val"] == True].copy()  # noqa: E712
+        else:
+            cut = int(len(df) * 0.8)
+            train_data, val_data = df.iloc[:cut].copy(), df.iloc[cut:].copy()
+        if cfg.enable_negative_sampling and "label" in train_data.columns:
+            train_data = self._apply_negative_sampling(train_data, cfg.negative_positive_ratio, "Training Set")
+        if cfg.enable_negative_sampling and "label" in val_data.columns and len(val_data) > 0:
+            val_data = self._apply_negative_sampling(val_data, cfg.negative_positive_ratio, "Validation Set")
+        uv, iv, cv = self._prepare_vocab_dicts()
+        if cfg.din_activation != "dice" or len(cfg.din_mlp_hidden_units) != 2:
+            raise NotImplementedError("DIN training implements Dice and two MLP hidden layers")
+        self.user_profile_features, self.item_features, self.context_features = list(uv), list(iv), list(cv)
+        self.encoder = DinEncoder(self.user_profile_dict, self.item_features_dict, self.user_history_dict,
+                                  self.user_profile_features, self.item_features, self.context_features,
+                                  self.label_encoders, cfg.din_seq_max_len)
+        self._tables = self.encoder.device_tables(torch.device(self.device))
+        enc = self._encode_frame(train_data)
+        labels = train_data["label"].to_numpy(np.float32)
+        val_enc = self._encode_frame(val_data) if len(val_data) > 0 else None
+        val_labels = val_data["label"].to_numpy(np.float32) if len(val_data) > 0 else None
+        self.loss_history, self.val_loss_history, self.final_metrics = [], [], None
+        init = self._init_state(uv, iv, cv)
+        val_probs = None
+        for epoch in range(cfg.epochs):
+            gen = torch.Generator(device=torch.device(self.device))
+            gen.manual_seed(int(cfg.random_seed) + epoch)
+            perm = torch.randperm(len(labels), device=torch.device(self.device), generator=gen)
+            before = len(self.loss_history)
+            self.train_on_encoded(enc, labels, cfg.batch_size, 1, cfg.learning_rate, order=perm.reshape(1, -1),
+                                  init_state=init if epoch == 0 else None)
+            n_b = len(self.loss_history) - before
+            self.loss_history[before:] = [(epoch + (i + 1) / n_b, v) for i, (_, v) in
+                                          enumerate(self.loss_history[before:])]
+            if val_enc is not None:
+                val_probs = self._scorer_from_trainer().predict(val_enc, cfg.batch_size)
+                loss, acc = _batched_bce(val_probs, val_labels, cfg.batch_size)
+                self.val_loss_history.append((epoch + 1, loss))
+                print(f"Epoch [{epoch + 1}/{cfg.epochs}] completed: Train Loss: "
+                      f"{np.mean([v for _, v in self.loss_history[before:]]):.4f}, Val Loss: {loss:.4f}, "
+                      f"Val Acc: {100 * acc:.2f}%")
+        self._scorer_from_trainer()
+        if val_probs is not None:
+            self.final_metrics = _validation_metrics(val_labels, val_probs)
+        os.makedirs(cfg.save_path, exist_ok=True)
+        with open(os.path.join(cfg.save_path, "label_encoders.pkl"), "wb") as f:
+            pickle.dump(self.label_encoders, f)
+        self.save_model()
+        return self
+
+    def save_model(self, save_dir=None):
+        """DIN.py:1285-1326: ``din_model.pth`` (the state_dict, DINModel's keys
+        and order), ``din_model_metadata.pkl`` and ``label_encoders.pkl`` in
+        the reference's formats; this ``load_model`` and the reference's read
+        them."""
+        from collections import OrderedDict
+
+        sd = self.state_dict()
+        save_dir = save_dir or self.config.save_path
+        os.makedirs(save_dir, exist_ok=True)
+        torch.save(OrderedDict(sd), os.path.join(save_dir, "din_model.pth"))
+        metadata = {"user_profile_features": self.user_profile_features, "item_features": self.item_features,
+                    "context_features": self.context_features, "din_embedding_dim": self.config.din_embedding_dim,
+                    "din_attention_hidden_units": self.config.din_attention_hidden_units,
+                    "din_mlp_hidden_units": self.config.din_mlp_hidden_units,
+                    "din_activation": self.config.din_activation, "din_seq_max_len": self.config.din_seq_max_len}
+        for name, obj in (("din_model_metadata.pkl", metadata), ("label_encoders.pkl", self.label_encoders)):
+            with open(os.path.join(save_dir, name), "wb") as f:
+                pickle.dump(obj, f)
+
     # --------------------------------------------------------- predict --
     def predict(self):
         """DIN.py:1219-1283: probabilities [len(main_df)] float32."""
+        if self.model is None and self.trainer is not None:
+            self._scorer_from_trainer()
         if self.model is None:
             raise ValueError("Model is not trained yet. Please train the model before prediction.")
         if not getattr(self, "label_encoders", None):
