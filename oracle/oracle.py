@@ -450,11 +450,13 @@ def fuse(methods, weights, strategy="weighted_avg", norm="local", topk=30, user_
 
 
 def ctx_features(main_users, main_items, main_scores, user_history, w2v, content, created, ctype, user_yt=None,
-                 art_yt=None, last_n=3, emb_dim=64):
+                 art_yt=None, last_n=3, emb_dim=64, content_dim=250, w2v_dim=None):
     """FeatureExtractor._extract_context_features
     (features/feature_extractor.py:440-723) restated in the reference's own
     numpy operations, per user group.  main_* are the main_df columns (str
-    user / item ids, float64 scores); returns {feature: column}."""
+    user / item ids, float64 scores); returns {feature: column}.  emb_dim is
+    the YouTubeDNN width (the reference's one zero default, :523), w2v_dim
+    the Word2Vec width when it differs, content_dim the content width."""
     import pandas as pd
 
     n = len(main_items)
@@ -469,7 +471,8 @@ def ctx_features(main_users, main_items, main_scores, user_history, w2v, content
     for u, h in user_history.items():  # :497-506
         ucats[u] = {ctype[i] for i in h if i in ctype}
     zid = np.zeros(emb_dim, dtype=np.float32)
-    zc = np.zeros(250, dtype=np.float32)
+    zw = zid if w2v_dim is None else np.zeros(w2v_dim, dtype=np.float32)
+    zc = np.zeros(content_dim, dtype=np.float32)
     groups = pd.Series(np.arange(n)).groupby(pd.Series(main_users)).apply(lambda s: s.to_numpy())
     items = np.asarray(main_items, dtype=object)
     for u, rows in groups.items():  # :527-690
@@ -483,7 +486,7 @@ def ctx_features(main_users, main_items, main_scores, user_history, w2v, content
             if ue is not None:
                 ie = np.array([art_yt.get(i, zid) for i in rec], dtype=np.float32)
                 ius[rows] = ie @ ue
-        rid = np.array([w2v.get(i, zid) for i in rec], dtype=np.float32)
+        rid = np.array([w2v.get(i, zw) for i in rec], dtype=np.float32)
         rc = np.array([content.get(i, zc) for i in rec], dtype=np.float32)
         rt = np.array([created.get(i, np.nan) for i in rec], dtype=np.float32)
         for k, h in enumerate(hist):
