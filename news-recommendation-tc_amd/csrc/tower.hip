@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
         for (int off = D; off < WAVE; off <<= 1) sum += __shfl_xor(sum, off, WAVE);
         // lane q < D holds x[q] = E_u[uid][q] and x[D + q] = mean[q]
         const float xm = sum / ((float)len + 1e-8f);
-        // layer 0: lane o (and o + 64) owns output o; same fma order as a
+        // layer 0: lane o (and o + 64) owns output o; same order as a
         // q-ascending dot (inputs broadcast from LDS)
         if (lane < D) {
             sx[lane] = xu;
@@ -110,11 +110,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
         __builtin_amdgcn_wave_barrier();
         float y0 = 0.0f, y1 = 0.0f;
         {
+            // product and sum rounded separately in every chain of both
+            // layers (see tt_user_mlp_kernel): left to the compiler, the
+            // 4-wide loops below became packed multiplies + adds, the
+            // h0 > 64 pair and layer 1's tail loop fmas
+#pragma clang fp contract(off)
             float z0 = lane < h0 ? sb0[lane] : 0.0f;
             float z1 = lane + WAVE < h0 ? sb0[lane + WAVE] : 0.0f;
             const float* wr0 = sw0 + (lane < h0 ? lane : 0) * S0;
             const float* wr1 = sw0 + (lane + WAVE < h0 ? lane + WAVE : 0) * S0;
-            // 4 inputs (broadcast) and 4 weights per LDS read; the fma
+            // 4 inputs (broadcast) and 4 weights per LDS read; the
             // chain still runs q = 0, 1, 2, ... in order.  Outputs 64 ..
             // only when h0 > 64 (round 6: the second chain ran, on row 0,
             // for every h0)
@@ -154,6 +159,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
         __builtin_amdgcn_wave_barrier();
         float v = 0.0f;
         {
+#pragma clang fp contract(off)
             float z = lane < h1 ? sb1[lane] : 0.0f;
             const float* wr = sw1 + (lane < h1 ? lane : 0) * S1;
             int q = 0;
@@ -188,8 +194,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
 // and re-normalisation as tt_user_kernel; the layers run from one packed
 // weight buffer (per layer W_l [w_l, in_l] row-major, then b_l [w_l]) read
 // through the caches, lane o owning outputs o, o + 64, ..., inputs broadcast
-// from a per-wave LDS row; each output is the same q-ascending fma chain as
-// the two-layer kernel.
+// from a per-wave LDS row; each output is the same q-ascending chain as the
+// two-layer kernel, z = z + w[q] * x[q] with the product rounded before the
+// sum (fp contract off in both), so [h0, D] gives the same bits from either.
 constexpr int TT_MAXL = 8, TT_MAXW = 256;
 struct TtLayers {
     int n;
@@ -233,6 +240,8 @@ __global__ __launch_bounds__(256) void tt_user_mlp_kernel(
             const int wo = ly.w[l];
             const float* bl = wl + (size_t)wo * in;
             for (int o = lane; o < wo; o += WAVE) {
+                // as in tt_user_kernel: the two kernels give the same bits
+#pragma clang fp contract(off)
                 float z = bl[o];
                 const float* wr = wl + (size_t)o * in;
                 for (int qq = 0; qq < in; ++qq) z += wr[qq] * sx[wave][cur][qq];

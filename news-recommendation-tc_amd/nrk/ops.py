@@ -53,11 +53,37 @@ def _finite(t, name):
 
 
 # ------------------------------------------------------------------ tower --
+def _tt_in_range(t, hi, what):
+    """One min / max reduction pair and one host read (a device sync)."""
+    if t.numel():
+        lo_v, hi_v = torch.stack([t.min(), t.max()]).tolist()
+        if lo_v < 0 or hi_v >= hi:
+            raise ValueError(f"{what} out of [0, {hi})")
+
+
+def tt_validate(uid, hist, hist_len, n_user_rows, n_item_rows):
+    """Raise ValueError unless hist_len is in [0, T], uid in [0, n_user_rows)
+    and every live history slot (t < hist_len[u]) in [0, n_item_rows): the
+    tower kernels gather without bounds checks.  Slots at or past hist_len
+    may hold anything (the kernels never use them as a row).  CPU or device
+    tensors; on the device this is a handful of reductions and syncs, meant to
+    run once per input set, outside any timed loop."""
+    n, T = hist.shape
+    if n == 0:
+        return
+    _tt_in_range(hist_len, T + 1, "hist_len")
+    _tt_in_range(uid, int(n_user_rows), "uid")
+    if T:
+        live = torch.arange(T, device=hist.device)[None, :] < hist_len[:, None]
+        _tt_in_range(torch.where(live, hist, torch.zeros((), dtype=hist.dtype, device=hist.device)),
+                     int(n_item_rows), "live hist entry")
+
+
 def tt_user_fwd(user_table, item_table, uid, hist, hist_len, w0, b0, w1, b1, validate: bool = True, out=None):
     """YoutubeDNN user tower + re-normalisation (youtubednn_recaller.py:129-178, :467-470).
-    ``validate`` checks hist_len against [0, T] (two device syncs); a caller
-    that re-runs the tower on inputs it already validated (the bench's timed
-    steps) may pass False.  ``out``: a preallocated fp32 [n, w1 rows] output
+    ``validate`` runs tt_validate (hist_len, uid and the live hist entries in
+    range: device syncs); a caller that re-runs the tower on inputs it already
+    validated (the bench's timed steps) may pass False.  ``out``: a preallocated fp32 [n, w1 rows] output
     (a pipelining caller's double buffer)."""
     _dev(user_table, item_table, uid, hist, hist_len, w0, b0, w1, b1)
     n, T = hist.shape
@@ -72,8 +98,8 @@ def tt_user_fwd(user_table, item_table, uid, hist, hist_len, w0, b0, w1, b1, val
     _need(b0, torch.float32, (h0,), "b0")
     _need(w1, torch.float32, (h1, h0), "w1")
     _need(b1, torch.float32, (h1,), "b1")
-    if validate and n and (int(hist_len.min()) < 0 or int(hist_len.max()) > T):
-        raise ValueError("hist_len out of [0, T]")
+    if validate:
+        tt_validate(uid, hist, hist_len, user_table.shape[0], item_table.shape[0])
     if out is None:
         out = torch.empty((n, h1), dtype=torch.float32, device=uid.device)
     else:
@@ -108,8 +134,7 @@ def tt_user_fwd_layers(user_table, item_table, uid, hist, hist_len, layers):
         widths.append(int(w.shape[0]))
         packed += [w.reshape(-1), b]
         fan_in = w.shape[0]
-    if n and (int(hist_len.min()) < 0 or int(hist_len.max()) > T):
-        raise ValueError("hist_len out of [0, T]")
+    tt_validate(uid, hist, hist_len, user_table.shape[0], item_table.shape[0])
     wts = torch.cat(packed).contiguous()
     out = torch.empty((n, D), dtype=torch.float32, device=uid.device)
     wv = (ctypes.c_int * len(widths))(*widths)
@@ -119,12 +144,15 @@ def tt_user_fwd_layers(user_table, item_table, uid, hist, hist_len, layers):
     return out
 
 
-def tt_item_fwd(item_table, ids):
-    """get_item_embedding + re-normalisation (youtubednn_recaller.py:184-188, :485-489)."""
+def tt_item_fwd(item_table, ids, validate: bool = True):
+    """get_item_embedding + re-normalisation (youtubednn_recaller.py:184-188, :485-489).
+    ``validate`` checks ids against [0, item rows) (one device sync)."""
     _dev(item_table, ids)
     _need(item_table, torch.float32, name="item_table")
     _need(ids, torch.int32, name="ids")
     n, D = ids.shape[0], item_table.shape[1]
+    if validate:
+        _tt_in_range(ids, item_table.shape[0], "ids")
     out = torch.empty((n, D), dtype=torch.float32, device=ids.device)
     _lib.call("nrk_tt_item_fwd", _ptr(item_table), item_table.shape[0], D, _ptr(ids), n,
               _ptr(out), _stream())

@@ -13,6 +13,9 @@ Each function restates the reference (file:line cited) in numpy / C:
                          -- EmbeddingSimilarity.calculate, similarity/embedding.py:35-62
 * ``tower_user``         -- YoutubeDNN.forward + _extract_embeddings re-norm, :129-178, :467-470
 * ``tower_item``         -- get_item_embedding + re-norm, :184-188, :485-489
+* ``tower_user_layers_f64`` / ``tower_item_f64``
+                         -- the same two expressions in float64 (the yardstick of
+                            tests/test_tower_host.py and tests/test_gpu_tower_shapes.py)
 * ``itemcf_sim``         -- ItemCFSimilarity.calculate, item_cf.py:17-89
 * ``itemcf_topn``        -- ItemCFRecaller._precompute_topk_similar_items, itemcf_recaller.py:41-54
 * ``itemcf_recall``      -- ItemCFRecaller.recall, itemcf_recaller.py:56-129
@@ -165,6 +168,56 @@ def tower_item(item_emb, ids):
     n = np.maximum(np.sqrt((x * x).sum(1, keepdims=True, dtype=f32)), f32(1e-12))
     x = (x / n).astype(f32)
     return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(f32)
+
+
+# --------------------------------------------------------------------------
+# Two-tower forward, the same expression in float64 (the bar's yardstick:
+# tests/test_tower_host.py measures the fp32 functions above against these)
+# --------------------------------------------------------------------------
+def tower_user_f64_parts(user_emb, item_emb, uid, hist, hist_len, layers, drop_last=False, len_plus=0):
+    """``tower_user_layers`` with every operation in float64 on the fp32
+    inputs.  Slots at or past ``hist_len`` are ignored by masking the indices
+    before the gather (their contents are never read as rows to add); the
+    divisor is float32(len) + float32(1e-8) widened.  Returns (out [n, D],
+    [z_l [n, w_l] per layer]: every layer before its ReLU).
+
+    Two deliberately wrong variants for the tests' sensitivity check:
+    ``drop_last`` leaves history slot len - 1 out of the sum, ``len_plus``
+    is added to the divisor's length."""
+    f64 = np.float64
+    hist_len = np.asarray(hist_len)
+    n, T = hist.shape
+    out = np.empty((n, layers[-1][0].shape[0]), f64)
+    pre = [np.empty((n, w.shape[0]), f64) for w, _ in layers]
+    for lo in range(0, n, 4096):  # bounds the [rows, T, D] float64 gather
+        sl = slice(lo, min(n, lo + 4096))
+        ln = hist_len[sl].astype(np.int64)
+        live = np.arange(T)[None, :] < (ln - (1 if drop_last else 0))[:, None]
+        he = item_emb[np.where(live, hist[sl], 0)].astype(f64)
+        ssum = np.where(live[:, :, None], he, 0.0).sum(1)
+        den = ((ln + len_plus).astype(np.float32) + np.float32(1e-8)).astype(f64)
+        x = np.concatenate([user_emb[uid[sl]].astype(f64), ssum / den[:, None]], 1)
+        for l, (w, b) in enumerate(layers):
+            pre[l][sl] = x @ w.astype(f64).T + b.astype(f64)
+            x = np.maximum(pre[l][sl], 0.0)
+        x = x / np.maximum(np.sqrt((x * x).sum(1, keepdims=True)), 1e-12)
+        n2 = np.sqrt((x * x).sum(1, keepdims=True))
+        n2[n2 == 0] = 1.0
+        out[sl] = x / n2
+    return out, pre
+
+
+def tower_user_layers_f64(user_emb, item_emb, uid, hist, hist_len, layers):
+    return tower_user_f64_parts(user_emb, item_emb, uid, hist, hist_len, layers)[0]
+
+
+def tower_item_f64(item_emb, ids):
+    """``tower_item`` in float64; like the reference (youtubednn_recaller.py:
+    487-489) the second division is unguarded: an all-zero row gives NaN."""
+    x = item_emb[ids].astype(np.float64)
+    x = x / np.maximum(np.sqrt((x * x).sum(1, keepdims=True)), 1e-12)
+    with np.errstate(invalid="ignore"):
+        return x / np.sqrt((x * x).sum(1, keepdims=True))
 
 
 # --------------------------------------------------------------------------

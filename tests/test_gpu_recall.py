@@ -277,7 +277,8 @@ def test_tower_vs_oracle(ops, D, h0):
     np.testing.assert_allclose(out.cpu().numpy(), ref, atol=1e-5, rtol=0)
 
 
-@pytest.mark.parametrize("widths", [[32], [64, 48, 32], [128, 96, 64, 32], [256, 32]])
+@pytest.mark.parametrize("widths", [[32], [64, 48, 32], [128, 96, 64, 32], [256, 32],
+                                    [64, 32], [100, 32], [128, 64], [3, 16]])  # the last four: two-layer shapes
 def test_tower_any_depth_vs_oracle(ops, widths):
     """youtubednn_hidden_units of any length (youtubednn_recaller.py:105-112)."""
     rng = np.random.default_rng(len(widths) * 11 + widths[0])
