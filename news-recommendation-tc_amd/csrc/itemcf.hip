@@ -240,8 +240,8 @@ __global__ __launch_bounds__(256) void cf_pairs_flat_kernel(
             lo = nlo;
         }
         // a window of 64 users' pair ends, one per lane; each lane finds its
-        // pair's user by a 6-step search over the window (shuffles), the
-        // window moving on to the last lane's user after every 64 pairs
+        // pair's user by a search over the window (shuffles), the window
+        // moving on to the last lane's user after every 64 pairs
         int64_t ub = lo;
         int64_t wend = ub + lane < n_users ? pair_off[ub + lane + 1] : INT64_MAX;
         int64_t cu = -1, b = 0, L = 1, base = 0;
@@ -256,6 +256,10 @@ __global__ __launch_bounds__(256) void cf_pairs_flat_kernel(
 #pragma unroll
                 for (int st = 32; st >= 1; st >>= 1)
                     if (__shfl(wend, k + st - 1, WAVE) <= p) k += st;
+                // the six steps rank p among the window's first 63 ends; its
+                // last end tells the window's last user from a later window
+                const int64_t wlast = __shfl(wend, 63, WAVE);
+                if (k == 63 && wlast <= p) k = 64;
                 if (u < 0 && k < 64) u = ub + k;
                 if (!__any(live && u < 0)) break;  // users with no pairs pushed a lane past the window
                 ub += 64;
