@@ -1130,9 +1130,10 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
         asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]));
 #endif
         TM_SSTAMP(10);
-        // epilogue: column sums of h and h^2 over the rows < c_t -- the
-        // lane's 4 rows in fp32 (relative error ~2^-22, below the reference's
-        // own fp32 statistics), then fp64; h of those rows to HBM, transposed
+        // epilogue: column sums of h and h^2 over the rows < c_t, every row
+        // in fp64 (4-row fp32 partials lost the variance of a column whose
+        // spread is small against its mean: sumsq - sum mean cancels, and a
+        // batch of two missed 1e-5 by 3 x); h of those rows to HBM, transposed
         // through the wave's LDS stage so each lane stores 16 contiguous bytes
         // of a row (3 wide stores per tile instead of 12 scattered ones)
         float* stg = hp + wv * (16 * DIN_H);
@@ -1147,10 +1148,12 @@ __global__ __launch_bounds__(TM_NT, 1) __attribute__((amdgpu_waves_per_eu(TM_NW 
                     if (jt < 2 || lr < DIN_H - 32) stg[(4 * lg + r) * DIN_H + 16 * jt + lr] = v[r];
                     if constexpr (!FULL) v[r] = 16 * j0.i + 4 * lg + r < j0.c ? v[r] : 0.0f;
                 }
-                const float s4 = (v[0] + v[1]) + (v[2] + v[3]);
-                const float q4 = fmaf(v[3], v[3], fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
-                ssum[jt] += (double)s4;
-                ssq[jt] += (double)q4;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double d = (double)v[r];
+                    ssum[jt] += d;
+                    ssq[jt] = fma(d, d, ssq[jt]);
+                }
             }
         };
         if (16 * (j0.i + 1) <= j0.c) epi(std::true_type{});  // uniform: a full tile
@@ -1308,13 +1311,14 @@ __global__ __launch_bounds__(256) void din_att_out_kernel(
             row[(n_user + n_ctx + n_item) * DIN_E + tid] = s;
             row[(n_user + n_ctx) * DIN_E + tid] =
                 tload(table + (row_base[n_user + f] + item_idx[b * n_item + f]) * DIN_E + e);
-        } else {
-            for (int i = tid - ID; i < (n_user + n_ctx) * DIN_E; i += 256 - ID) {
-                const int f = i / DIN_E, e = i % DIN_E;
-                const int64_t r = f < n_user ? row_base[f] + user_idx[b * n_user + f]
-                                             : row_base[n_item + f] + ctx_idx[b * n_ctx + (f - n_user)];
-                row[i] = tload(table + r * DIN_E + e);
-            }
+        }
+        // every thread: with 8 item features ID is the whole workgroup, so the
+        // user / context columns cannot be left to the threads past ID
+        for (int i = tid; i < (n_user + n_ctx) * DIN_E; i += 256) {
+            const int f = i / DIN_E, e = i % DIN_E;
+            const int64_t r = f < n_user ? row_base[f] + user_idx[b * n_user + f]
+                                         : row_base[n_item + f] + ctx_idx[b * n_ctx + (f - n_user)];
+            row[i] = tload(table + r * DIN_E + e);
         }
     }
 }

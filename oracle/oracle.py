@@ -20,6 +20,8 @@ Each function restates the reference (file:line cited) in numpy / C:
 * ``itemcf_topn``        -- ItemCFRecaller._precompute_topk_similar_items, itemcf_recaller.py:41-54
 * ``itemcf_recall``      -- ItemCFRecaller.recall, itemcf_recaller.py:56-129
 * ``din_forward``        -- Dice / ActivationUnit / DINModel.forward, DIN.py:29-286
+* ``din_forward_f64``    -- the same in float64, per Dice batch (the yardstick of
+                            tests/test_din_host.py and tests/test_gpu_din_shapes.py)
 * ``fuse``               -- RecallFusion.fuse, recall/fusion.py:67-342
 * ``ctx_features``       -- FeatureExtractor._extract_context_features,
                             features/feature_extractor.py:440-723
@@ -382,6 +384,157 @@ def din_forward(sd, user, item, hist, ctx, mask, feats, round_bf16=False):
     logit = (x @ sd["mlp.4.weight"].astype(f32).T + sd["mlp.4.bias"].astype(f32)).astype(f32)[:, 0]
     prob = (1.0 / (1.0 + np.exp(-logit.astype(np.float64)))).astype(f32)
     return prob, logit, w
+
+
+# --------------------------------------------------------------------------
+# DIN forward, the same expression in float64 (the bar's yardstick:
+# tests/test_din_host.py measures din_forward above against it)
+# --------------------------------------------------------------------------
+def _pow2_scale(mx):
+    """The kernels' power-of-two scale: max |x| in [2^(e-1), 2^e) -> 2^(14-e)."""
+    return 1.0 if not mx > 0 else float(np.ldexp(1.0, 14 - int(np.frexp(np.float32(mx))[1])))
+
+
+def _fp16_at(x, s):
+    """x rounded to the nearest fp16 at the power-of-two scale s."""
+    with np.errstate(over="ignore"):
+        return (np.asarray(x, np.float64) * s).astype(np.float16).astype(np.float64) / s
+
+
+def _din_batch_f64(tabs, W, user, item, hist, ctx, mask, mut, stats=None):
+    """One Dice batch of ``din_forward_f64``.  ``stats``: per Dice layer the
+    (mean, std) to normalise with instead of the batch's own.  Returns
+    (probs, logits, att, [(mean, std) per Dice layer])."""
+    f64 = np.float64
+    tu, ti, tc = tabs
+    B, T = mask.shape
+    ddof = mut.get("ddof", 1)
+    used = []
+
+    def dice(x, for_stats=None):
+        """Dice (DIN.py:39-44): batch mean and std over axis 0."""
+        given = stats[len(used)] if stats is not None else None
+        if given is not None:
+            mean, std = given
+        else:
+            xs = x if for_stats is None else for_stats
+            with np.errstate(invalid="ignore", divide="ignore"):
+                mean, std = xs.mean(0, keepdims=True), xs.std(0, ddof=ddof, keepdims=True)
+        used.append((mean, std))
+        with np.errstate(over="ignore"):
+            p = 1.0 / (1.0 + np.exp(-((x - mean) / (std + 1e-8))))
+        return p * x + (1.0 - p) * 0.01 * x
+
+    cat = lambda ts, idx: np.concatenate([t[idx[..., n]] for n, t in enumerate(ts)], -1)  # noqa: E731
+    U, Q = cat(tu, user), cat(ti, item)
+    C = cat(tc, ctx) if tc else np.zeros((B, 0), f64)
+    h = np.empty((B, T, W["a0b"].shape[0]), f64)
+    K = np.empty((B, T, Q.shape[1]), f64)
+    for lo in range(0, B, 4096):  # bounds the [rows, T, 4d] concatenation (DIN.py:105-114)
+        sl = slice(lo, min(B, lo + 4096))
+        k = cat(ti, hist[sl])
+        q = np.broadcast_to(Q[sl, None, :], k.shape)
+        qk = q * k
+        if mut.get("p_lo_dropped"):
+            qk = _fp16_at(qk, mut["_s_tab"] ** 2)
+        h[sl] = np.concatenate([k, q, q - k, qk], 2) @ W["a0w"].T + W["a0b"]
+        K[sl] = k
+    hs = None
+    if mut.get("pad_row_zero"):
+        hs = np.where(((mask == 0) & (hist == 0).all(2))[:, :, None], 0.0, h)
+    w = (dice(h, hs) @ W["a2w"].T + W["a2b"])[:, :, 0] * mask.astype(f64)  # DIN.py:114-124
+    if mut.get("drop_last"):
+        live = mask != 0
+        last = T - 1 - np.argmax(live[:, ::-1], 1)
+        rows = np.flatnonzero(live.any(1))
+        w[rows, last[rows]] = 0.0
+    wh = (w[:, :, None] * K).sum(1)  # DIN.py:276
+    x = np.concatenate([U, C, Q, wh], 1)  # DIN.py:279
+    x = dice(x @ W["m0w"].T + W["m0b"])
+    x = dice(x @ W["m2w"].T + W["m2b"])
+    logit = (x @ W["m4w"].T + W["m4b"])[:, 0]
+    with np.errstate(over="ignore"):
+        prob = 1.0 / (1.0 + np.exp(-logit))
+    return prob, logit, w, used
+
+
+def din_forward_f64(sd, user, item, hist, ctx, mask, feats, round_bf16=False, batch_size=None, **mutations):
+    """``din_forward`` (DIN.py:29-44 Dice, :105-124 ActivationUnit, :214-286
+    DINModel.forward) with every operation in float64 on the fp32 (or
+    bf16-rounded) parameters.  ``batch_size``: the samples are consecutive
+    Dice batches of that many rows (DINRanker.predict's loop, DIN.py:1245-1283),
+    gathered and scored one batch at a time; a batch of one row is NaN.
+    Returns (probs [B], logits [B], att [B, T]) in float64.
+
+    Deliberately wrong variants for tests/test_din_host.py's sensitivity check:
+    ``drop_last`` zeroes the attention weight of the last position with a
+    non-zero mask; ``ddof=0`` is the biased std; ``w0_hi_only`` /
+    ``w1_hi_only`` keep only the fp16 part of mlp.0 / mlp.2's weight at the
+    kernels' power-of-two scale (max |W| < 2^14); ``p_lo_dropped`` rounds q*k
+    to fp16 at the position-major kernel's scale s^2 (max |table| s in
+    [2^6, 2^7)); ``neighbour_stats=l`` normalises Dice layer l (0: attention,
+    1, 2: the MLP) of batch s with the statistics batch s+1 has in a correct
+    run (the last with the first's); ``pad_row_zero`` takes the attention
+    hidden rows of padding positions (mask 0, every index 0) as 0 in the
+    column statistics."""
+    f64 = np.float64
+    uf, itf, cf = feats
+
+    def tab(group, f):
+        w = sd[f"{group}.{f}.weight"].astype(np.float32)
+        return (bf16_round(w) if round_bf16 else w).astype(f64)
+
+    tabs = ([tab("user_profile_embedding_dict", f) for f in uf], [tab("item_embedding_dict", f) for f in itf],
+            [tab("context_embedding_dict", f) for f in cf])
+    g = lambda k: np.asarray(sd[k], np.float32).astype(f64)  # noqa: E731
+    W = {"a0w": g("activation_unit.mlp.0.weight"), "a0b": g("activation_unit.mlp.0.bias"),
+         "a2w": g("activation_unit.mlp.2.weight"), "a2b": g("activation_unit.mlp.2.bias")}
+    for li in (0, 2, 4):
+        W[f"m{li}w"], W[f"m{li}b"] = g(f"mlp.{li}.weight"), g(f"mlp.{li}.bias")
+    mut = dict(mutations)
+    unknown = set(mut) - {"drop_last", "ddof", "w0_hi_only", "w1_hi_only", "p_lo_dropped", "neighbour_stats",
+                          "pad_row_zero"}
+    assert not unknown, unknown
+    for key, name in (("w0_hi_only", "m0w"), ("w1_hi_only", "m2w")):
+        if mut.get(key):
+            W[name] = _fp16_at(W[name], _pow2_scale(np.abs(W[name]).max()))
+    if mut.get("p_lo_dropped"):
+        mut["_s_tab"] = _pow2_scale(max(np.abs(t).max() for grp in tabs for t in grp)) / 128.0
+    N, T = mask.shape
+    S = N if batch_size is None or batch_size >= N else int(batch_size)
+    segs = [slice(s, min(N, s + S)) for s in range(0, N, S)]
+    prob, logit, att = np.empty(N, f64), np.empty(N, f64), np.empty((N, T), f64)
+
+    def run(sl, stats=None):
+        if sl.stop - sl.start < 2 and mut.get("ddof", 1) == 1:  # torch.std of one row (DIN.py:41)
+            return np.full(1, np.nan), np.full(1, np.nan), np.full((1, T), np.nan), None
+        return _din_batch_f64(tabs, W, user[sl], item[sl], hist[sl], ctx[sl], mask[sl], mut, stats)
+
+    nb = mut.get("neighbour_stats")
+    if nb is None or nb is False:
+        for sl in segs:
+            prob[sl], logit[sl], att[sl], _ = run(sl)
+        return prob, logit, att
+    own = [run(sl)[3] for sl in segs]
+    for n, sl in enumerate(segs):
+        if own[n] is None or own[(n + 1) % len(segs)] is None:  # a batch of one row has no statistics
+            prob[sl], logit[sl], att[sl], _ = run(sl)
+            continue
+        st = list(own[n])
+        st[int(nb)] = own[(n + 1) % len(segs)][int(nb)]
+        # later layers keep this batch's own statistics of its (now different) values
+        prob[sl], logit[sl], att[sl], _ = run(sl, _StatsFrom(st, int(nb)))
+    return prob, logit, att
+
+
+class _StatsFrom:
+    """Dice statistics override for layer ``l`` only (None elsewhere)."""
+
+    def __init__(self, st, l):
+        self.st, self.l = st, l
+
+    def __getitem__(self, n):
+        return self.st[n] if n == self.l else None
 
 
 class DinTorchCPU:
