@@ -522,6 +522,21 @@ __device__ __forceinline__ void dma_piece(const uint8_t* src, uint8_t* dst) {
                                      (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
 }
 
+// dma_piece with the source as a wave-uniform address sbase (a scalar register
+// pair, the load's base) + this lane's byte offset voff, to the wave-uniform
+// LDS address dst (m0; one wait state between its write and the load): no
+// vector instruction forms an address.  The load counts on vmcnt like
+// dma_piece's; the callers wait for it themselves.  m0 is the compiler's own
+// (not a clobber it accepts): it writes m0 in front of each use of its own,
+// and a kernel that calls this must have none (ip_scan_ws_kernel: no other
+// LDS-DMA, no indirect register indexing; check the listing).
+__device__ __forceinline__ void dma_piece_s(const uint8_t* sbase, uint32_t voff, uint32_t dst) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0"
+                 :
+                 : "s"(sbase), "v"(voff), "s"(dst)
+                 : "memory");
+}
+
 // DS = 2: block b + 1's fragments (at LDS address base) are read while block
 // b's MFMAs run -- the wait for block b's data and the issue of block b + 1's
 // reads are one asm statement whose operands tie both register sets, so
@@ -542,6 +557,22 @@ __device__ __forceinline__ void pf_wait_issue(u32x4 (&cur)[2], uint32_t base, u3
 }
 __device__ __forceinline__ void pf_wait(u32x4 (&cur)[2]) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1])::"memory");
+}
+// the same two with the block's place as an immediate offset OFF from one base
+// register (ip_scan_ws_kernel: the blocks of a step are contiguous in the ring)
+template <int OFF>
+__device__ __forceinline__ void pf_issue_at(uint32_t base, u32x4 (&af)[2]) {
+    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
+                 : "=&v"(af[0]), "=&v"(af[1])
+                 : "v"(base), "n"(OFF), "n"(OFF + 1024)
+                 : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void pf_wait_issue_at(u32x4 (&cur)[2], uint32_t base, u32x4 (&nxt)[2]) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6"
+                 : "=&v"(nxt[0]), "=&v"(nxt[1]), "+v"(cur[0]), "+v"(cur[1])
+                 : "v"(base), "n"(OFF), "n"(OFF + 1024)
+                 : "memory");
 }
 
 // The scan (every shape but the warp-specialized one below): workgroup ub
@@ -1033,8 +1064,9 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
     const int pw = wv & (NPW - 1);
     const int ubase = (int)blockIdx.x * (NPW * UG * 32) + pw * (UG * 32);
 #if NRK_SCAN_STAMP
-    // dev stamps (waves 0 and 4): 0 sync; MFMA wave: 1 tile, 7 maxima write
-    // + issue, 2 end; book wave: 1 maxima read, 2 appends, 4 inserts, 5 loop
+    // dev stamps (waves 0 and 4): 0 sync; MFMA wave: 3 step head (barrier ->
+    // first MFMA), 1 tile (first MFMA -> last maxima write), 7 loop, 2 end;
+    // book wave: 1 maxima read, 2 appends, 4 inserts, 5 loop
     uint64_t sstp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_prev = __builtin_readcyclecounter();
     auto stamp_out = [&]() {
@@ -1057,23 +1089,26 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
     const int tail_blk = n_items >> 5;
     const int full_tiles = tail_blk / TB;
     const int last_tile = (nblk - 1) / TB;
-    // MFMA wave wv loads pieces LPW wv .. LPW wv + LPW - 1 of every tile
-    // (dma_piece; the tile clamped as in ip_scan_kernel's issue_tile)
-    auto issue_tile = [&](int tt, int sl) {
-        const uint32_t ttc = (uint32_t)min(tt, last_tile);
+    // MFMA wave wv loads pieces LPW wv .. LPW wv + LPW - 1 of every tile (the
+    // tile clamped as in ip_scan_kernel's issue_tile).  A step's TPS LPW pieces
+    // go by their source addresses, which the wave forms one step before it
+    // issues them (step_srcs: scalar work only; the clamp of piece_src is one
+    // s_min -- offsets and the body are multiples of 1 KB), to the ring half
+    // rh (byte offset of the step's first slot) by dma_piece_s.
+    constexpr int SPC = TPS * LPW;
+    const uint32_t pc0 = (uint32_t)(wv * LPW) * 1024u;
+    auto step_srcs = [&](const int (&tt)[TPS], const uint8_t* (&o)[SPC]) {
 #pragma unroll
-        for (int c = 0; c < LPW; ++c) {
-            const int piece = wv * LPW + c;
-            dma_piece(piece_src(catalog, ttc * (uint32_t)TILE_BYTES + (uint32_t)piece * 1024u, body_bytes, lane),
-                      smem + sl * TILE_BYTES + piece * 1024);
-        }
+        for (int j = 0; j < SPC; ++j)
+            o[j] = catalog + min((uint32_t)min(tt[j / LPW], last_tile) * (uint32_t)TILE_BYTES + pc0 +
+                                     (uint32_t)(j % LPW) * 1024u,
+                                 (uint32_t)body_bytes - 1024u);
+#pragma unroll
+        for (int j = 0; j < SPC; ++j) asm volatile("" : "+s"(o[j]));  // formed here, not sunk to the caller's tail
     };
-    auto issue_step = [&](int p) {  // the TPS tiles of step p (past the end: dummies, uniform vmcnt)
-#pragma unroll
-        for (int t = 0; t < TPS; ++t) {
-            const int i = TPS * p + t;
-            issue_tile(seq(min(i, nseq - 1)), i % NSL);
-        }
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    auto issue_piece = [&](const uint8_t* const (&o)[SPC], uint32_t rh, int j) {
+        dma_piece_s(o[j], lane16, lds_base + rh + pc0 + (uint32_t)((j / LPW) * TILE_BYTES + (j % LPW) * 1024));
     };
     // MFMA waves: own pieces of this step's tiles landed (DAHEAD - 1 steps
     // still in flight), the previous step's maxima written; book waves: their
@@ -1096,17 +1131,23 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
                                 live);
         }
         __builtin_amdgcn_s_setprio(SCAN_WS_PRIO);
+        static_assert(NSL == 2 * TPS, "a step is one half of the ring: its TPS TB blocks are contiguous");
         const uint32_t lds0 = lds_base + lane * 16;
-        // LDS address of this lane's fragments of block b of ring slot sl
-        auto frag_base = [&](int sl, int b) -> uint32_t { return lds0 + (uint32_t)(sl * TILE_BYTES + b * DS * 1024); };
-        // tile tt in ring slot sl -> the half-block maxima, written to maxima
-        // slot ms block by block (software pipeline of ip_scan_kernel's tile():
-        // step j = (block, group) issues its MFMAs while step j - 2 reduces;
-        // block b's maxima are complete after step 8 b + 9)
-        // NT tiles (tt[t] in ring slot sl[t], maxima to slot ms[t]) as one
-        // software pipeline over their NT TB blocks: no refill between them
-        auto tile = [&](auto nt_c, const int (&tt)[TPS], const int (&sl)[TPS], const uint32_t (&ms)[TPS],
-                        auto mask_c) __attribute__((always_inline)) {
+        // the tiles tt of a step, in the ring half whose fragments of this lane
+        // start at LDS address fb -> the half-block maxima, written to the
+        // maxima slots at ms (tile t: + t MXS) block by block (software pipeline
+        // of ip_scan_kernel's tile(): step j = (block, group) issues its MFMAs
+        // while step j - 2 reduces; block b's maxima are complete after step
+        // 8 b + 9).  NT tiles as one software pipeline over their NT TB blocks:
+        // no refill between them; block bb's fragments sit at fb + 2048 bb, an
+        // immediate offset of the reads.  The first instructions are block 0's
+        // fragment reads; the next step's LDS-DMA pieces (dma(j), j < SPC) go
+        // out behind them, under the reads' latency (one piece behind the first
+        // MFMA of each of blocks 0 .. 3 instead measured the same within the
+        // run-to-run spread).  mid() is the caller's scalar
+        // bookkeeping, run once, between two blocks of the MFMA stream.
+        auto tile = [&](auto nt_c, const int (&tt)[TPS], uint32_t fb, uint32_t ms, auto mask_c, auto&& dma,
+                        auto&& mid) __attribute__((always_inline)) {
             constexpr int NT = decltype(nt_c)::value, NBK = NT * TB;
             constexpr bool MASK = decltype(mask_c)::value;
             float mx[2][UG];  // by block parity
@@ -1138,24 +1179,25 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
             auto red2 = [&](const P5& pm, int bb, int gg) __attribute__((always_inline)) {
                 mx[bb & 1][gg] = fmaxf(fmaxf(fmaxf(fmaxf(pm[0], pm[1]), pm[2]), pm[3]), pm[4]);  // 2 v_max3
             };
-            auto put = [&](int bb) __attribute__((always_inline)) {
+            auto put = [&](auto bc) __attribute__((always_inline)) {
+                constexpr int bb = decltype(bc)::value;
                 const f32x4 v0 = {mx[bb & 1][0], mx[bb & 1][1], mx[bb & 1][2], mx[bb & 1][3]};
                 const f32x4 v1 = {mx[bb & 1][4], mx[bb & 1][5], mx[bb & 1][6], mx[bb & 1][7]};
-                asm volatile("ds_write_b128 %0, %1 offset:0\n\tds_write_b128 %0, %2 offset:1024" ::"v"(
-                                 ms[bb / TB] + (uint32_t)((bb % TB) * 2048)),
-                             "v"(v0), "v"(v1)
+                const uint32_t a = ms + (uint32_t)((bb / TB) * MXS);
+                asm volatile("ds_write_b128 %0, %1 offset:%3\n\tds_write_b128 %0, %2 offset:%4" ::"v"(a), "v"(v0),
+                             "v"(v1), "n"((bb % TB) * 2048), "n"((bb % TB) * 2048 + 1024)
                              : "memory");
             };
-            auto slb = [&](int bb) { return sl[bb / TB]; };
             constexpr int NSTEP = NBK * UG;
             f32x16 acc[2];
             float pm[2][5];  // partial maxima by step parity
             u32x4 afp[DS], afb[DS];
-            pf_issue(frag_base(slb(0), 0), afp);
+            pf_issue_at<0>(fb, afp);
+            static_for<SPC>([&](auto jc) { dma(decltype(jc)::value); });
             static_for<NBK>([&](auto bc) {
                 constexpr int bb = decltype(bc)::value;
                 u32x4 afn[DS];
-                if constexpr (bb + 1 < NBK) pf_wait_issue(afp, frag_base(slb(bb + 1), (bb + 1) % TB), afn);
+                if constexpr (bb + 1 < NBK) pf_wait_issue_at<(bb + 1) * DS * 1024>(afp, fb, afn);
                 else pf_wait(afp);
 #pragma unroll
                 for (int s = 0; s < DS; ++s) afb[s] = afp[s];
@@ -1163,8 +1205,10 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
 #pragma unroll
                     for (int s = 0; s < DS; ++s) afp[s] = afn[s];
                 }
+                if constexpr (bb == 0) SC_STAMP(3);  // block 0's fragments are here: the step's first MFMA is next
                 static_for<UG>([&](auto gc) {
                     constexpr int g = decltype(gc)::value, j = bb * UG + g;
+                    if constexpr (g == 0 && bb == 1) mid();  // every piece is out
                     f32x16& A = acc[j & 1];
                     A = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afb[0]), ufrag[g][0],
                                                                f32x16{}, 0, 0, 0);
@@ -1176,7 +1220,8 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
                     A = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afb[1]), ufrag[g][1], A, 0,
                                                                0, 0);
                     if constexpr (j >= 1) red1(acc[(j - 1) & 1], (j - 1) / UG, pm[(j - 1) & 1]);
-                    if constexpr (bb > 0 && g == 2) put(bb - 1);  // block bb - 1 complete (its last red2 at g = 1)
+                    // block bb - 1 complete (its last red2 at g = 1)
+                    if constexpr (bb > 0 && g == 2) put(std::integral_constant<int, bb - 1>{});
                     if constexpr (!MASK) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                         if constexpr (j >= 1) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
@@ -1187,35 +1232,115 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
             red2(pm[(NSTEP - 2) & 1], (NSTEP - 2) / UG, (NSTEP - 2) % UG);
             red1(acc[(NSTEP - 1) & 1], (NSTEP - 1) / UG, pm[(NSTEP - 1) & 1]);
             red2(pm[(NSTEP - 1) & 1], (NSTEP - 1) / UG, (NSTEP - 1) % UG);
-            put(NBK - 1);
+            put(std::integral_constant<int, NBK - 1>{});
         };
+        // Step bookkeeping, ahead of its use and wave-uniform (SGPRs), so that
+        // a barrier is followed by block 0's fragment reads at once (the head
+        // used to recompute all of this: ~90 instructions and ten branches in
+        // front of the first MFMA, 10.6 % of the step): ct = the tiles of the step the
+        // wave runs next, full = none of them holds rows past the catalog,
+        // hp = its ring half (byte offset; its maxima slots sit at MXS /
+        // TILE_BYTES times that); nt = the tiles of the step after, no = the
+        // source addresses of this wave's pieces of them, issued behind the
+        // barrier in front of step ct.  Once those pieces are out, advance()
+        // (tile()'s mid: straight-line scalar code in the shadow of the MFMA
+        // stream) forms the tiles of the step after that (ft) and their
+        // addresses (no again); the tail of a step (roll) only moves ft -> nt
+        // -> ct.  The sequence is seq() for the first two steps only; a later
+        // step is (sx, sx + d1), and sx moves on by d2: (pstride, 2 pstride)
+        // in the pre-pass, (1, 2) in the main pass, both clamped to the
+        // range's last tile -- past the end that is the dummy seq(min(i, nseq
+        // - 1)) names.  Only the step at the change-over (step PAm) differs,
+        // and retarget() -- the one branch of the tail, taken twice a launch
+        // -- sets it up: with n_pre even it restarts sx at tile_lo, with n_pre
+        // odd it is (the last pre-pass tile, tile_lo) and sx goes on at
+        // tile_lo + 1.
+        static_assert(TPS == 2 && DAHEAD == 1, "the step sequence below: two tiles a step, one step ahead");
+        auto seq_c = [&](int i) { return seq(min(i, nseq - 1)); };
+        const int hi1 = tile_hi - 1, PAm = n_pre / TPS;
+        int ct[TPS] = {seq_c(0), seq_c(1)}, nt[TPS] = {seq_c(TPS), seq_c(TPS + 1)}, ft[TPS] = {0, 0};
+        const uint8_t* no[SPC];
+        step_srcs(ct, no);
 #pragma unroll
-        for (int p = 0; p < DAHEAD; ++p) issue_step(p);
-        for (int p = 0; p <= NP; ++p) {
+        for (int j = 0; j < SPC; ++j) issue_piece(no, 0u, j);  // step 0
+        step_srcs(nt, no);
+        int rl = (PAm < 2 ? -4 : PAm) - 2;  // steps to form before the change-over step (never: negative)
+        int sx = PAm < 2 ? tile_lo + 2 * TPS - n_pre : tile_lo + 2 * TPS * pstride;
+        int d1 = PAm < 2 ? 1 : pstride, d2 = TPS * d1;
+        auto retarget = [&]() {
+            if (__builtin_expect((unsigned)(rl + 1) <= 1u, 0)) {  // the change-over step is next, or was last
+                if (rl < 0) {
+                    d1 = 1;
+                    d2 = TPS;
+                } else if (n_pre & 1) {
+                    d1 = tile_lo - sx;
+                    d2 = d1 + 1;
+                } else {
+                    sx = tile_lo;
+                    d1 = 1;
+                    d2 = TPS;
+                }
+            }
+        };
+        retarget();
+        auto advance = [&]() {
+            ft[0] = min(sx, hi1);
+            ft[1] = min(sx + d1, hi1);
+            sx += d2;
+            --rl;
+            step_srcs(ft, no);
+        };
+        constexpr uint32_t HALF = TPS * TILE_BYTES;
+        uint32_t hp = 0u;
+        bool full = max(ct[0], ct[1]) < full_tiles;
+        auto dma = [&](int j) { issue_piece(no, hp ^ HALF, j); };
+        auto roll = [&]() {
+#pragma unroll
+            for (int t = 0; t < TPS; ++t) {
+                ct[t] = nt[t];
+                nt[t] = ft[t];
+            }
+            full = max(ct[0], ct[1]) < full_tiles;
+            hp ^= HALF;
+            retarget();
+        };
+        const int NPF = nseq / TPS;  // whole steps: one pipeline over their TPS tiles
+        for (int p = 0; p < NPF; ++p) {
+            SC_STAMP(7);
+            const uint32_t fb = lds0 + hp, ms = mx_base + hp * (uint32_t)(MXS / TILE_BYTES);
+            // the body is chosen in front of the barrier: behind it the first
+            // instructions are the fragment reads
+            if (__builtin_expect(!full, 0)) {
+                sync();
+                SC_STAMP(0);
+                tile(std::integral_constant<int, TPS>{}, ct, fb, ms, std::true_type{}, dma, advance);
+                SC_STAMP(1);
+                roll();
+                continue;
+            }
+            sync();
+            SC_STAMP(0);
+            tile(std::integral_constant<int, TPS>{}, ct, fb, ms, std::false_type{}, dma, advance);
+            SC_STAMP(1);
+            roll();
+        }
+        if (nseq % TPS) {  // a short last step: its first tile
             SC_STAMP(7);
             sync();
             SC_STAMP(0);
-            issue_step(p + DAHEAD);
-            int tts[TPS], sls[TPS];
-            uint32_t mss[TPS];
-#pragma unroll
-            for (int t = 0; t < TPS; ++t) {
-                const int i = min(TPS * p + t, nseq - 1);
-                tts[t] = seq(i);
-                sls[t] = (TPS * p + t) % NSL;
-                mss[t] = mx_base + (uint32_t)(((p & 1) * TPS + t) * MXS);
-            }
-            if (TPS * p + TPS <= nseq) {  // a whole step: one pipeline over its TPS tiles
-                bool full = true;
-#pragma unroll
-                for (int t = 0; t < TPS; ++t) full = full && tts[t] < full_tiles;
-                if (full) tile(std::integral_constant<int, TPS>{}, tts, sls, mss, std::false_type{});
-                else tile(std::integral_constant<int, TPS>{}, tts, sls, mss, std::true_type{});
-            } else if (TPS * p < nseq) {  // a short last step: its first tile
-                tile(std::integral_constant<int, 1>{}, tts, sls, mss, std::true_type{});
-            }
+            tile(std::integral_constant<int, 1>{}, ct, lds0 + hp, mx_base + hp * (uint32_t)(MXS / TILE_BYTES),
+                 std::true_type{}, dma, advance);
             SC_STAMP(1);
+            roll();
         }
+        // the last barrier publishes the last step's maxima; the pieces behind
+        // it are dummies like every piece past the end (uniform vmcnt)
+        SC_STAMP(7);
+        sync();
+        SC_STAMP(0);
+#pragma unroll
+        for (int j = 0; j < SPC; ++j) dma(j);
+        SC_STAMP(1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if NRK_SCAN_STAMP
         SC_STAMP(2);
