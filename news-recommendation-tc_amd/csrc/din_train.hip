@@ -41,8 +41,7 @@
 // that p (1 - p) underflows in BCELoss (|x| >~ 15).  Loss and gradients stay
 // finite in both cases; parity with torch is not claimed.
 //
-// tr_adam of tower_train.hip is restated here (dt_adam) rather than shared
-// through a header, so that tower_train.hip compiles exactly as before.
+// The Adam sweep is train_common.h's, with one table.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -51,6 +50,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "din_common.h"
+#include "train_common.h"
 
 namespace nrk {
 
@@ -692,72 +692,7 @@ __global__ __launch_bounds__(256) void dt_emb_long_kernel(const int32_t* __restr
     }
 }
 
-// ------------------------------------------------------------------- Adam --
-// torch/optim/adam.py _single_tensor_adam, as tt_adam_kernel (tower_train.hip)
-struct DtAdamK {
-    float w1, beta2, w2, bc2_sqrt, eps, neg_step;
-};
-__device__ __forceinline__ void dt_adam(float& p, float& m, float& v, float g, const DtAdamK& k) {
-#pragma clang fp contract(off)
-    m = __fmaf_rn(k.w1, g - m, m);
-    v = __fmaf_rn(k.w2 * g, g, v * k.beta2);
-    const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-    p = p + (k.neg_step * m) / denom;
-}
-
-// Blocks [0, wblocks): the packed weights, dense g.  Then the table, one
-// float4 per thread; a row's gradient by binary search in the compact list
-// (absent: g = 0; with m = v = 0 as well the row is left untouched).
-__global__ __launch_bounds__(256) void dt_adam_kernel(float* __restrict__ w, float* __restrict__ w_m,
-                                                      float* __restrict__ w_v, const float* __restrict__ w_g,
-                                                      int64_t n_w, int wblocks, float* __restrict__ tp,
-                                                      float* __restrict__ tm, float* __restrict__ tv,
-                                                      int64_t n_rows, const int32_t* __restrict__ rows,
-                                                      const float* __restrict__ vals,
-                                                      const int32_t* __restrict__ count, DtAdamK k) {
-    int64_t blk = blockIdx.x;
-    if (blk < wblocks) {
-        const int64_t e = blk * 256 + threadIdx.x;
-        if (e < n_w) {
-            float p = w[e], m = w_m[e], v = w_v[e];
-            dt_adam(p, m, v, w_g[e], k);
-            w[e] = p;
-            w_m[e] = m;
-            w_v[e] = v;
-        }
-        return;
-    }
-    blk -= wblocks;
-    const int64_t e4 = blk * 256 + threadIdx.x;  // float4 index, 8 per row
-    const int64_t row = e4 >> 3;
-    if (row >= n_rows) return;
-    int lo = 0, hi = *count;
-    const int n = hi;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (rows[mid] < row) lo = mid + 1;
-        else hi = mid;
-    }
-    const bool has = lo < n && rows[lo] == row;
-    float4 m = reinterpret_cast<float4*>(tm)[e4], v = reinterpret_cast<float4*>(tv)[e4];
-    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (has) g = reinterpret_cast<const float4*>(vals)[(int64_t)lo * 8 + (e4 & 7)];
-    else if (m.x == 0.0f && m.y == 0.0f && m.z == 0.0f && m.w == 0.0f && v.x == 0.0f && v.y == 0.0f &&
-             v.z == 0.0f && v.w == 0.0f)
-        return;
-    float4 p = reinterpret_cast<float4*>(tp)[e4];
-    dt_adam(p.x, m.x, v.x, g.x, k);
-    dt_adam(p.y, m.y, v.y, g.y, k);
-    dt_adam(p.z, m.z, v.z, g.z, k);
-    dt_adam(p.w, m.w, v.w, g.w, k);
-    reinterpret_cast<float4*>(tp)[e4] = p;
-    reinterpret_cast<float4*>(tm)[e4] = m;
-    reinterpret_cast<float4*>(tv)[e4] = v;
-}
-
 // ------------------------------------------------------------------- host --
-static inline size_t dt_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct DtShape {
     int Fu, NI, Fc, H1, H2, B, T, Di, IN, S;
     int64_t R, N;
@@ -847,54 +782,48 @@ static int dt_sort_bits(int64_t R) {
 
 static DtWs dt_layout(void* base, const DtShape& s) {
     DtWs w{};
-    char* p = static_cast<char*>(base);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = p ? p + o : nullptr;
-        o += dt_al(bytes);
-        return r;
-    };
+    Arena a(base);
     const size_t f = sizeof(float), B = s.B, C = (size_t)s.T * 36;
     w.nblk = (s.B + DT_CB - 1) / DT_CB;
     w.ksplit = std::max(1, std::min(16, s.B / 256));
-    w.z = (float*)take(f * B * C);
-    w.mu_a = (double*)take(8 * C);
-    w.sd_a = (double*)take(8 * C);
-    w.S_a = (double*)take(8 * 3 * C);
-    w.wbuf = (float*)take(f * B * s.T);
-    w.ds = (float*)take(f * B * s.T);
-    w.dsT = (float*)take(f * s.T);
-    w.Abuf = (float*)take(f * B * 36);
-    w.Gq = (float*)take(f * 36 * s.Di);
-    w.gpart = (double*)take(8 * (size_t)w.nblk * 2 * 36 * s.Di);
-    w.x0 = (float*)take(f * B * s.IN);
-    w.dx0 = (float*)take(f * B * s.IN);
-    w.z1 = (float*)take(f * B * s.H1);
-    w.mu1 = (double*)take(8 * (size_t)s.H1);
-    w.sd1 = (double*)take(8 * (size_t)s.H1);
-    w.a1 = (float*)take(f * B * s.H1);
-    w.da1 = (float*)take(f * B * s.H1);
-    w.S1 = (double*)take(8 * 3 * (size_t)s.H1);
-    w.z2 = (float*)take(f * B * s.H2);
-    w.mu2 = (double*)take(8 * (size_t)s.H2);
-    w.sd2 = (double*)take(8 * (size_t)s.H2);
-    w.da2 = (float*)take(f * B * s.H2);
-    w.S2 = (double*)take(8 * 3 * (size_t)s.H2);
-    w.hb = (float*)take(f * B * (s.H2 + 1));
-    w.loss_b = (float*)take(f * B);
-    w.gemm_part = (double*)take(8 * (size_t)w.ksplit * std::max({s.H1, s.H2, 36}) * std::max(s.IN, s.H1));
-    w.dk = (float*)take(f * B * s.T * s.Di);
-    w.epart = (double*)take(8 * 2 * 32 * (size_t)((s.N + DT_PIECE - 1) / DT_PIECE));
-    w.keys = (uint32_t*)take(4 * (size_t)s.N);
-    w.keys2 = (uint32_t*)take(4 * (size_t)s.N);
-    w.cid = (int32_t*)take(4 * (size_t)s.N);
-    w.cid2 = (int32_t*)take(4 * (size_t)s.N);
-    w.flag = (int32_t*)take(4 * (size_t)s.N);
-    w.seg = (int32_t*)take(4 * (size_t)s.N);
-    w.starts = (int32_t*)take(4 * (size_t)(s.N + 1));
+    w.z = (float*)a.take(f * B * C);
+    w.mu_a = (double*)a.take(8 * C);
+    w.sd_a = (double*)a.take(8 * C);
+    w.S_a = (double*)a.take(8 * 3 * C);
+    w.wbuf = (float*)a.take(f * B * s.T);
+    w.ds = (float*)a.take(f * B * s.T);
+    w.dsT = (float*)a.take(f * s.T);
+    w.Abuf = (float*)a.take(f * B * 36);
+    w.Gq = (float*)a.take(f * 36 * s.Di);
+    w.gpart = (double*)a.take(8 * (size_t)w.nblk * 2 * 36 * s.Di);
+    w.x0 = (float*)a.take(f * B * s.IN);
+    w.dx0 = (float*)a.take(f * B * s.IN);
+    w.z1 = (float*)a.take(f * B * s.H1);
+    w.mu1 = (double*)a.take(8 * (size_t)s.H1);
+    w.sd1 = (double*)a.take(8 * (size_t)s.H1);
+    w.a1 = (float*)a.take(f * B * s.H1);
+    w.da1 = (float*)a.take(f * B * s.H1);
+    w.S1 = (double*)a.take(8 * 3 * (size_t)s.H1);
+    w.z2 = (float*)a.take(f * B * s.H2);
+    w.mu2 = (double*)a.take(8 * (size_t)s.H2);
+    w.sd2 = (double*)a.take(8 * (size_t)s.H2);
+    w.da2 = (float*)a.take(f * B * s.H2);
+    w.S2 = (double*)a.take(8 * 3 * (size_t)s.H2);
+    w.hb = (float*)a.take(f * B * (s.H2 + 1));
+    w.loss_b = (float*)a.take(f * B);
+    w.gemm_part = (double*)a.take(8 * (size_t)w.ksplit * std::max({s.H1, s.H2, 36}) * std::max(s.IN, s.H1));
+    w.dk = (float*)a.take(f * B * s.T * s.Di);
+    w.epart = (double*)a.take(8 * 2 * 32 * (size_t)((s.N + DT_PIECE - 1) / DT_PIECE));
+    w.keys = (uint32_t*)a.take(4 * (size_t)s.N);
+    w.keys2 = (uint32_t*)a.take(4 * (size_t)s.N);
+    w.cid = (int32_t*)a.take(4 * (size_t)s.N);
+    w.cid2 = (int32_t*)a.take(4 * (size_t)s.N);
+    w.flag = (int32_t*)a.take(4 * (size_t)s.N);
+    w.seg = (int32_t*)a.take(4 * (size_t)s.N);
+    w.starts = (int32_t*)a.take(4 * (size_t)(s.N + 1));
     w.sort_tmp_bytes = dt_sort_tmp_bound(s.N);
-    w.sort_tmp = take(w.sort_tmp_bytes);
-    w.bytes = o;
+    w.sort_tmp = a.take(w.sort_tmp_bytes);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -1052,20 +981,11 @@ int nrk_din_adam_step(float* weights, float* w_m, float* w_v, const float* w_gra
     if (dim != DIN_E) NRK_UNSUPPORTED("training is built for din_embedding_dim == 32");
     NRK_REQUIRE(n_weights > 0 && n_weights < ((int64_t)1 << 31), "bad n_weights");
     NRK_REQUIRE(n_table_rows > 0 && n_table_rows <= (int64_t)INT32_MAX / 32, "bad n_table_rows");
-    NRK_REQUIRE(t >= 1, "t is the 1-based step number");
-    NRK_REQUIRE(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
-                "bad hyper-parameters");
+    AdamK k;
+    if (const int rc = adam_scalars(__func__, lr, beta1, beta2, eps, t, &k)) return rc;
     NRK_REQUIRE(weights && w_m && w_v && w_grad && table && t_m && t_v && t_rows && t_vals && t_count, "null pointer");
-    // the scalars as _single_tensor_adam forms them, in double, then one rounding to fp32
-    const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
-    const DtAdamK k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)std::sqrt(bc2), (float)eps,
-                    (float)(-(lr / bc1))};
-    const int wblocks = (int)((n_weights + 255) / 256);
-    const int64_t tblocks = (n_table_rows * 8 + 255) / 256;
-    dt_adam_kernel<<<(unsigned)(wblocks + tblocks), 256, 0, as_stream(stream)>>>(
-        weights, w_m, w_v, w_grad, n_weights, wblocks, table, t_m, t_v, n_table_rows, t_rows, t_vals, t_count, k);
-    NRK_CHECK_LAUNCH();
-    return NRK_OK;
+    const AdamSegs<1> seg{{{table, t_m, t_v, t_rows, t_vals, t_count, n_table_rows}}};
+    return adam_sweep<DIN_E>(__func__, weights, w_m, w_v, w_grad, n_weights, seg, k, as_stream(stream));
 }
 
 }  // extern "C"

@@ -40,7 +40,28 @@ void clear_error();
         }                                                                           \
     } while (0)
 
+// the macros' error for a check that lives in a helper: fn is the entry point's name
+inline int fail_as(const char* fn, int rc, const char* msg) {
+    set_error(std::string(fn) + ": " + msg);
+    return rc;
+}
+
 inline hipStream_t as_stream(nrk_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ------------------------------------------------------------ workspaces --
+// Host only.  Carves a caller's workspace into pieces, each rounded up to 256
+// bytes.  With a null base (the size query) every piece is null and `bytes`
+// counts the same.
+struct Arena {
+    char* base;
+    size_t bytes = 0;
+    explicit Arena(void* b) : base(static_cast<char*>(b)) {}
+    void* take(size_t n) {
+        void* r = base ? base + bytes : nullptr;
+        bytes += (n + 255) & ~(size_t)255;
+        return r;
+    }
+};
 
 constexpr int WAVE = 64;
 

@@ -5,13 +5,9 @@
 // re-normalisation of :467-470.  Item tower: get_item_embedding (:184-188)
 // fused with :485-489.  Memory-bound gathers (1 + T rows of D fp32 per user)
 // feeding a 2-layer MLP that fits in LDS; one wave per user.
-#include "nrk_common.h"
+#include "tower_common.h"
 
 namespace nrk {
-
-#ifndef NRK_TT_CH
-#define NRK_TT_CH 8
-#endif
 
 template <int D>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void tt_user_kernel(
@@ -47,9 +43,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
     // history rows in flight per lane (a config-2 user, T = 30 at D = 32, has
     // up to 15 per lane: two rounds).  All 16 at once measured slower in the
     // bench (tower 0.330-0.334 vs 0.294-0.295 ms, one box, two pairs): a
-    // round issues CH unconditional loads per lane, and most histories are
-    // short (dev A/B: -DNRK_TT_CH=16)
-    constexpr int CH = NRK_TT_CH;
+    // round issues CH unconditional loads per lane, and most histories are short
+    constexpr int CH = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int d = lane % D, ph = lane / D;
     const int64_t wstride = (int64_t)gridDim.x * 4;
@@ -189,20 +184,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
     if (pu >= 0 && lane < h1) out[pu * h1 + lane] = pout;
 }
 
-// Any depth (youtubednn_hidden_units is a list, youtubednn_recaller.py:105-112):
-// user_tower = [Linear(in_l, w_l), ReLU, Dropout] per layer.  Same gather
-// and re-normalisation as tt_user_kernel; the layers run from one packed
+// Any depth (TtLayers, tower_common.h).  Same gather (tt_hist_mean) and
+// re-normalisation as tt_user_kernel; the layers run from one packed
 // weight buffer (per layer W_l [w_l, in_l] row-major, then b_l [w_l]) read
 // through the caches, lane o owning outputs o, o + 64, ..., inputs broadcast
 // from a per-wave LDS row; each output is the same q-ascending chain as the
 // two-layer kernel, z = z + w[q] * x[q] with the product rounded before the
 // sum (fp contract off in both), so [h0, D] gives the same bits from either.
-constexpr int TT_MAXL = 8, TT_MAXW = 256;
-struct TtLayers {
-    int n;
-    int w[TT_MAXL];
-};
-
 template <int D>
 __global__ __launch_bounds__(256) void tt_user_mlp_kernel(
     const float* __restrict__ user_table, const float* __restrict__ item_table,
@@ -210,25 +198,12 @@ __global__ __launch_bounds__(256) void tt_user_mlp_kernel(
     const int32_t* __restrict__ hist_len, int64_t n, int T, const float* __restrict__ wts, TtLayers ly,
     float* __restrict__ out) {
     __shared__ float sx[4][2][TT_MAXW > 2 * D ? TT_MAXW : 2 * D];
-    constexpr int P = WAVE / D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int d = lane % D, ph = lane / D;
     const int64_t wstride = (int64_t)gridDim.x * 4;
     for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u < n; u += wstride) {
-        const int len = hist_len[u];
         const int32_t hv = lane < T ? hist[u * T + lane] : 0;
-        const float xu = user_table[(int64_t)uid[u] * D + d];
-        float sum = 0.0f;
-        const int nit = (len + P - 1) / P;
-        for (int i = 0; i < nit; ++i) {
-            const int t = ph + P * i;
-            const int32_t r = __shfl(hv, t < T ? t : 0, WAVE);
-            const float v = item_table[(int64_t)(t < len ? r : 0) * D + d];
-            if (t < len) sum += v;  // t ascending
-        }
-#pragma unroll
-        for (int off = D; off < WAVE; off <<= 1) sum += __shfl_xor(sum, off, WAVE);
-        const float xm = sum / ((float)len + 1e-8f);
+        const float xu = user_table[(int64_t)uid[u] * D + lane % D];
+        const float xm = tt_hist_mean<D>(item_table, hv, hist_len[u], T, lane);
         if (lane < D) {
             sx[wave][0][lane] = xu;
             sx[wave][0][D + lane] = xm;
@@ -294,13 +269,9 @@ __global__ __launch_bounds__(256) void tt_item_kernel(const float* __restrict__ 
 using namespace nrk;
 
 // workgroups of 256 threads resident at once on the device (occupancy API x
-// CUs), at most one per 4 users; dev A/B: -DNRK_TT_GRID=2048 (the old fixed grid)
-#ifndef NRK_TT_GRID
-#define NRK_TT_GRID 0
-#endif
+// CUs), at most one per 4 users
 static int tt_grid(const void* fn, size_t lds, int64_t n) {
     int per_cu = 0, dev = 0, cus = 256;
-    if (NRK_TT_GRID > 0) return (int)std::min<int64_t>((n + 3) / 4, NRK_TT_GRID);
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)per_cu * std::max(cus, 1)));
@@ -316,10 +287,9 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
     clear_error();
     NRK_REQUIRE(n >= 0 && seq_len >= 1 && seq_len <= 64, "bad sizes (seq_len must be in [1, 64])");
     NRK_REQUIRE(n_user_rows > 0 && n_item_rows > 0, "empty embedding tables");
-    if (!(dim == 16 || dim == 32 || dim == 64)) NRK_UNSUPPORTED("dim must be 16, 32 or 64");
+    if (const int rc = tt_check_shape(__func__, dim)) return rc;
     NRK_REQUIRE(h0 >= 1 && h0 <= 128, "h0 must be in [1, 128]");
-    NRK_REQUIRE(h1 == dim, "last hidden width must equal the embedding dim "
-                           "(youtubednn_recaller.py:461-465)");
+    NRK_REQUIRE(h1 == dim, TT_LAST_WIDTH);
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(user_table && item_table && uid && hist && hist_len && w0 && b0 && w1 && b1 && out,
                 "null pointer");
@@ -330,18 +300,14 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
     // persistent grid of resident workgroups only (the weights' LDS admits ~5
     // per CU): a grid larger than the resident set left the queued
     // workgroups to run after the first ones finished, on a thinner machine
-#define NRK_TT_LAUNCH(DD)                                                                      \
-    do {                                                                                       \
-        (void)hipFuncSetAttribute((const void*)tt_user_kernel<DD>,                                 \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-        const int grid = tt_grid((const void*)tt_user_kernel<DD>, lds, n);                      \
-        tt_user_kernel<DD><<<grid, 256, lds, s>>>(user_table, item_table, uid, hist, hist_len, \
-                                                  n, seq_len, w0, b0, h0, w1, b1, h1, out);    \
-    } while (0)
-    if (dim == 16) NRK_TT_LAUNCH(16);
-    else if (dim == 32) NRK_TT_LAUNCH(32);
-    else NRK_TT_LAUNCH(64);
-#undef NRK_TT_LAUNCH
+    tt_for_dim(dim, [&](auto dc) {
+        constexpr int DD = decltype(dc)::value;
+        (void)hipFuncSetAttribute((const void*)tt_user_kernel<DD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        const int grid = tt_grid((const void*)tt_user_kernel<DD>, lds, n);
+        tt_user_kernel<DD><<<grid, 256, lds, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, w0, b0, h0,
+                                                  w1, b1, h1, out);
+    });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -353,24 +319,16 @@ int nrk_tt_user_fwd_layers(const float* user_table, int64_t n_user_rows, const f
     clear_error();
     NRK_REQUIRE(n >= 0 && seq_len >= 1 && seq_len <= 64, "bad sizes (seq_len must be in [1, 64])");
     NRK_REQUIRE(n_user_rows > 0 && n_item_rows > 0, "empty embedding tables");
-    if (!(dim == 16 || dim == 32 || dim == 64)) NRK_UNSUPPORTED("dim must be 16, 32 or 64");
-    NRK_REQUIRE(widths != nullptr, "null widths");
-    if (n_layers < 1 || n_layers > TT_MAXL) NRK_UNSUPPORTED("1 to 8 hidden layers are compiled");
     TtLayers ly{};
-    ly.n = n_layers;
-    for (int l = 0; l < n_layers; ++l) {
-        if (widths[l] < 1 || widths[l] > TT_MAXW) NRK_UNSUPPORTED("hidden widths must be in [1, 256]");
-        ly.w[l] = widths[l];
-    }
-    NRK_REQUIRE(widths[n_layers - 1] == dim, "last hidden width must equal the embedding dim "
-                                             "(youtubednn_recaller.py:461-465)");
+    if (const int rc = tt_check_shape(__func__, dim, n_layers, widths, &ly)) return rc;
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(user_table && item_table && uid && hist && hist_len && weights && out, "null pointer");
     hipStream_t s = as_stream(stream);
     const int grid = (int)std::min<int64_t>((n + 3) / 4, 2048);
-    if (dim == 16) tt_user_mlp_kernel<16><<<grid, 256, 0, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, weights, ly, out);
-    else if (dim == 32) tt_user_mlp_kernel<32><<<grid, 256, 0, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, weights, ly, out);
-    else tt_user_mlp_kernel<64><<<grid, 256, 0, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, weights, ly, out);
+    tt_for_dim(dim, [&](auto dc) {
+        tt_user_mlp_kernel<decltype(dc)::value><<<grid, 256, 0, s>>>(user_table, item_table, uid, hist, hist_len, n,
+                                                                     seq_len, weights, ly, out);
+    });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -379,14 +337,12 @@ int nrk_tt_item_fwd(const float* item_table, int64_t n_item_rows, int dim, const
                     int64_t n, float* out, nrk_stream_t stream) {
     clear_error();
     NRK_REQUIRE(n >= 0 && n_item_rows > 0, "bad sizes");
-    if (!(dim == 16 || dim == 32 || dim == 64)) NRK_UNSUPPORTED("dim must be 16, 32 or 64");
+    if (const int rc = tt_check_shape(__func__, dim)) return rc;
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(item_table && ids && out, "null pointer");
     hipStream_t s = as_stream(stream);
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    if (dim == 16) tt_item_kernel<16><<<grid, 256, 0, s>>>(item_table, ids, n, out);
-    else if (dim == 32) tt_item_kernel<32><<<grid, 256, 0, s>>>(item_table, ids, n, out);
-    else tt_item_kernel<64><<<grid, 256, 0, s>>>(item_table, ids, n, out);
+    tt_for_dim(dim, [&](auto dc) { tt_item_kernel<decltype(dc)::value><<<grid, 256, 0, s>>>(item_table, ids, n, out); });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }

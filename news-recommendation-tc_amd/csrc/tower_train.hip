@@ -16,20 +16,18 @@
 //                            (row, contribution) sorted in LDS, one sum per
 //                            destination row in ascending contribution order
 //  (4. mark / count / compact / merge only when the batch spans several chunks)
-//   5. tt_adam_kernel        one sweep over weights and both tables
+//   5. adam_sweep_kernel     one sweep over weights and both tables
+//                            (train_common.h)
 // No floating-point atomics anywhere, so every output is bitwise reproducible.
 #include <algorithm>
 
-#include "nrk_common.h"
+#include "tower_common.h"
+#include "train_common.h"
 
 namespace nrk {
 
-constexpr int TR_MAXL = 8, TR_MAXW = 256, TR_MAXB = 8192, TR_MAXT = 64;
+constexpr int TR_MAXB = 8192, TR_MAXT = 64;
 constexpr int TR_KEYS = 8192;  // keys one workgroup sorts in LDS (6 bytes each)
-struct TrLayers {
-    int n;
-    int w[TR_MAXL];
-};
 
 // ------------------------------------------------------------ generator --
 // Counter-based: a pure function of (seed, a, b, c, d), splitmix64's
@@ -61,16 +59,16 @@ static inline uint32_t tr_threshold(float p) {
 template <int D>
 __global__ __launch_bounds__(256) void tt_train_fb_kernel(
     const float* __restrict__ user_table, const float* __restrict__ item_table, const float* __restrict__ wts,
-    TrLayers ly, const int64_t* __restrict__ log_off, const int32_t* __restrict__ log_items,
+    TtLayers ly, const int64_t* __restrict__ log_off, const int32_t* __restrict__ log_items,
     const int32_t* __restrict__ s_user, const int32_t* __restrict__ s_pos, const int32_t* __restrict__ s_target,
     const float* __restrict__ s_label, int B, int T, float scale, uint32_t thr, uint64_t seed, uint64_t step,
     int asz, int dsz, int staged, float* __restrict__ loss_b, float* __restrict__ act, float* __restrict__ delta,
     float* __restrict__ gU, float* __restrict__ gH, float* __restrict__ gT) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* sa = lds + wave * (asz + 2 * TR_MAXW);
-    float* sd[2] = {sa + asz, sa + asz + TR_MAXW};
-    float* sw = lds + 4 * (asz + 2 * TR_MAXW);
+    float* sa = lds + wave * (asz + 2 * TT_MAXW);
+    float* sd[2] = {sa + asz, sa + asz + TT_MAXW};
+    float* sw = lds + 4 * (asz + 2 * TT_MAXW);
     if (staged) {
         int in = 2 * D;
         const float* src = wts;
@@ -87,8 +85,6 @@ __global__ __launch_bounds__(256) void tt_train_fb_kernel(
     }
     const float* wbase = staged ? sw : wts;
     const int pad = staged ? 1 : 0;
-    constexpr int P = WAVE / D;
-    const int d = lane % D, ph = lane / D;
     const float invB = 1.0f / (float)B;
     for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
         const int u = s_user[b];
@@ -97,22 +93,13 @@ __global__ __launch_bounds__(256) void tt_train_fb_kernel(
         const float y = s_label[b];
         const int64_t base = log_off[u];
         const int32_t hv = lane < len ? log_items[base + lane] : 0;
-        const float xu = user_table[(int64_t)u * D + d];
+        const float xu = user_table[(int64_t)u * D + lane % D];
         const float tv = lane < D ? item_table[(int64_t)tgt * D + lane] : 0.0f;
-        float sum = 0.0f;
-        const int nit = (len + P - 1) / P;
-        for (int i = 0; i < nit; ++i) {
-            const int t = ph + P * i;
-            const int32_t r = __shfl(hv, t < len ? t : 0, WAVE);
-            const float v = item_table[(int64_t)r * D + d];
-            if (t < len) sum += v;  // t ascending, as the forward kernels
-        }
-#pragma unroll
-        for (int off = D; off < WAVE; off <<= 1) sum += __shfl_xor(sum, off, WAVE);
-        const float cnt = (float)len + 1e-8f;
+        const float xm = tt_hist_mean<D>(item_table, hv, len, len, lane);
+        const float cnt = (float)len + 1e-8f;  // the mean's denominator, again in the backward
         if (lane < D) {
             sa[lane] = xu;
-            sa[D + lane] = sum / cnt;
+            sa[D + lane] = xm;
         }
         wave_sync_lds();
         // forward: A_{l+1} = dropout(relu(W_l A_l + b_l))
@@ -125,6 +112,7 @@ __global__ __launch_bounds__(256) void tt_train_fb_kernel(
             float* o_ = sa + aoff + in;
             const uint64_t key = thr ? tr_key(seed, step, (uint32_t)l, (uint32_t)b) : 0;
             for (int o = lane; o < wo; o += WAVE) {
+                // not shared with the forward kernels: theirs run with contraction off, this one may fuse
                 float z = bl[o];
                 const float* wr = wl + (size_t)o * ws;
                 for (int q = 0; q < in; ++q) z += wr[q] * a[q];
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(256) void tt_train_fb_kernel(
 // The last block reduces the per-sample losses the same way.
 __global__ __launch_bounds__(1024) void tt_wgrad_kernel(const float* __restrict__ act,
                                                         const float* __restrict__ delta,
-                                                        const float* __restrict__ loss_b, TrLayers ly, int D,
+                                                        const float* __restrict__ loss_b, TtLayers ly, int D,
                                                         int B, int asz, int dsz, int n_w,
                                                         float* __restrict__ w_grad, float* __restrict__ loss) {
     __shared__ float part[16][64];
@@ -501,87 +489,7 @@ __global__ __launch_bounds__(256) void tt_emb_merge_kernel(TrTable tu, TrTable t
     }
 }
 
-// ---------------------------------------------------------------- 5. Adam --
-// torch/optim/adam.py _single_tensor_adam, fp32 element by element:
-//   m.lerp_(g, 1 - beta1)            fma(w, g - m, m)
-//   v.mul_(beta2).addcmul_(g, g, 1 - beta2)
-//                                    fma((1 - beta2) g, g, beta2 v)
-//   denom = sqrt(v) / sqrt(bc2) + eps
-//   p.addcdiv_(m, denom, -lr / bc1)  p + (value m) / denom
-// The two fused multiply-adds are where torch's CPU kernels fuse (lerp's
-// vec::fmadd, addcmul's contracted self + value t1 t2: found by replaying
-// the step in numpy against torch.optim.Adam); contraction is off
-// so that nothing else is fused.
-struct AdamK {
-    float w1, beta2, w2, bc2_sqrt, eps, neg_step;
-};
-__device__ __forceinline__ void tr_adam(float& p, float& m, float& v, float g, const AdamK& k) {
-#pragma clang fp contract(off)
-    m = __fmaf_rn(k.w1, g - m, m);
-    v = __fmaf_rn(k.w2 * g, g, v * k.beta2);
-    const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-    p = p + (k.neg_step * m) / denom;
-}
-
-struct AdamSeg {
-    float *p, *m, *v;
-    const int32_t* rows;
-    const float* vals;
-    const int32_t* count;
-    int64_t n_rows;
-};
-
-// Blocks [0, wblocks): the packed weights, one element per thread, dense g.
-// Then the user table, then the item table: one float4 per thread; the row's
-// gradient is found by binary search in the compact list (absent: g = 0).
-__global__ __launch_bounds__(256) void tt_adam_kernel(float* __restrict__ w, float* __restrict__ w_m,
-                                                      float* __restrict__ w_v, const float* __restrict__ w_g,
-                                                      int64_t n_w, int wblocks, AdamSeg su, AdamSeg si,
-                                                      int64_t ublocks, int D, AdamK k) {
-    int64_t blk = blockIdx.x;
-    if (blk < wblocks) {
-        const int64_t e = blk * 256 + threadIdx.x;
-        if (e < n_w) {
-            float p = w[e], m = w_m[e], v = w_v[e];
-            tr_adam(p, m, v, w_g[e], k);
-            w[e] = p;
-            w_m[e] = m;
-            w_v[e] = v;
-        }
-        return;
-    }
-    blk -= wblocks;
-    const AdamSeg sg = blk < ublocks ? su : si;
-    if (blk >= ublocks) blk -= ublocks;
-    const int64_t e4 = blk * 256 + threadIdx.x;  // float4 index
-    const int q = D / 4;
-    const int64_t row = e4 / q;
-    if (row >= sg.n_rows) return;
-    int lo = 0, hi = *sg.count;
-    const int n = hi;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sg.rows[mid] < row) lo = mid + 1;
-        else hi = mid;
-    }
-    const bool has = lo < n && sg.rows[lo] == row;
-    float4 m = reinterpret_cast<float4*>(sg.m)[e4], v = reinterpret_cast<float4*>(sg.v)[e4];
-    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (has) g = reinterpret_cast<const float4*>(sg.vals)[(int64_t)lo * q + e4 % q];
-    else if (m.x == 0.0f && m.y == 0.0f && m.z == 0.0f && m.w == 0.0f && v.x == 0.0f && v.y == 0.0f &&
-             v.z == 0.0f && v.w == 0.0f)
-        return;  // m = v = g = 0: the update changes nothing
-    float4 p = reinterpret_cast<float4*>(sg.p)[e4];
-    tr_adam(p.x, m.x, v.x, g.x, k);
-    tr_adam(p.y, m.y, v.y, g.y, k);
-    tr_adam(p.z, m.z, v.z, g.z, k);
-    tr_adam(p.w, m.w, v.w, g.w, k);
-    reinterpret_cast<float4*>(sg.p)[e4] = p;
-    reinterpret_cast<float4*>(sg.m)[e4] = m;
-    reinterpret_cast<float4*>(sg.v)[e4] = v;
-}
-
-// ------------------------------------------------------------- 6. dropout --
+// ------------------------------------------------------------- 5. dropout --
 __global__ __launch_bounds__(256) void tt_dropout_mask_kernel(uint64_t seed, uint64_t step, int layer, int batch,
                                                               int width, uint32_t thr, float* __restrict__ out) {
     const int64_t n = (int64_t)batch * width;
@@ -591,7 +499,7 @@ __global__ __launch_bounds__(256) void tt_dropout_mask_kernel(uint64_t seed, uin
     }
 }
 
-// ------------------------------------------------------------- 7. samples --
+// ------------------------------------------------------------- 6. samples --
 __device__ __forceinline__ int64_t tr_n_pos(int64_t n) {
     if (n < 2) return 0;
     const int64_t test = std::max<int64_t>(1, (int64_t)((double)n * 0.2));  // max(1, int(n * 0.2))
@@ -653,8 +561,6 @@ __global__ __launch_bounds__(256) void tt_make_samples_kernel(
 }
 
 // ------------------------------------------------------------------ host --
-static inline size_t tr_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct TrWs {
     float *loss_b, *act, *delta, *gU, *gH, *gT;
     int32_t *crow_u, *ccnt_u, *crow_i, *ccnt_i, *mark_u, *mark_i, *blk_u, *blk_i;
@@ -663,7 +569,7 @@ struct TrWs {
     size_t mark_bytes, bytes;
 };
 
-static TrWs tr_layout(void* base, int64_t U, int64_t I, int D, const TrLayers& ly, int T, int B) {
+static TrWs tr_layout(void* base, int64_t U, int64_t I, int D, const TtLayers& ly, int T, int B) {
     TrWs w{};
     w.asz = 2 * D;
     for (int l = 0; l < ly.n; ++l) {
@@ -673,57 +579,37 @@ static TrWs tr_layout(void* base, int64_t U, int64_t I, int D, const TrLayers& l
     w.CS = std::min(256, TR_KEYS / (T + 1));
     w.n_chunks = (B + w.CS - 1) / w.CS;
     w.cap_i = w.CS * (T + 1);
-    char* p = static_cast<char*>(base);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = p ? p + o : nullptr;
-        o += tr_al(bytes);
-        return r;
-    };
-    w.loss_b = (float*)take(sizeof(float) * B);
-    w.act = (float*)take(sizeof(float) * (size_t)B * w.asz);
-    w.delta = (float*)take(sizeof(float) * (size_t)B * w.dsz);
-    w.gU = (float*)take(sizeof(float) * (size_t)B * D);
-    w.gH = (float*)take(sizeof(float) * (size_t)B * D);
-    w.gT = (float*)take(sizeof(float) * (size_t)B * D);
+    Arena a(base);
+    w.loss_b = (float*)a.take(sizeof(float) * B);
+    w.act = (float*)a.take(sizeof(float) * (size_t)B * w.asz);
+    w.delta = (float*)a.take(sizeof(float) * (size_t)B * w.dsz);
+    w.gU = (float*)a.take(sizeof(float) * (size_t)B * D);
+    w.gH = (float*)a.take(sizeof(float) * (size_t)B * D);
+    w.gT = (float*)a.take(sizeof(float) * (size_t)B * D);
     if (w.n_chunks > 1) {
-        w.crow_u = (int32_t*)take(sizeof(int32_t) * (size_t)w.n_chunks * w.CS);
-        w.cval_u = (float*)take(sizeof(float) * (size_t)w.n_chunks * w.CS * D);
-        w.ccnt_u = (int32_t*)take(sizeof(int32_t) * w.n_chunks);
-        w.crow_i = (int32_t*)take(sizeof(int32_t) * (size_t)w.n_chunks * w.cap_i);
-        w.cval_i = (float*)take(sizeof(float) * (size_t)w.n_chunks * w.cap_i * D);
-        w.ccnt_i = (int32_t*)take(sizeof(int32_t) * w.n_chunks);
-        w.mark_u = (int32_t*)take(sizeof(int32_t) * (size_t)(U + I));  // mark_u | mark_i: one memset
+        w.crow_u = (int32_t*)a.take(sizeof(int32_t) * (size_t)w.n_chunks * w.CS);
+        w.cval_u = (float*)a.take(sizeof(float) * (size_t)w.n_chunks * w.CS * D);
+        w.ccnt_u = (int32_t*)a.take(sizeof(int32_t) * w.n_chunks);
+        w.crow_i = (int32_t*)a.take(sizeof(int32_t) * (size_t)w.n_chunks * w.cap_i);
+        w.cval_i = (float*)a.take(sizeof(float) * (size_t)w.n_chunks * w.cap_i * D);
+        w.ccnt_i = (int32_t*)a.take(sizeof(int32_t) * w.n_chunks);
+        w.mark_u = (int32_t*)a.take(sizeof(int32_t) * (size_t)(U + I));  // mark_u | mark_i: one memset
         w.mark_i = w.mark_u ? w.mark_u + U : nullptr;
         w.mark_bytes = sizeof(int32_t) * (size_t)(U + I);
-        w.blk_u = (int32_t*)take(sizeof(int32_t) * (size_t)((U + TR_CT - 1) / TR_CT));
-        w.blk_i = (int32_t*)take(sizeof(int32_t) * (size_t)((I + TR_CT - 1) / TR_CT));
+        w.blk_u = (int32_t*)a.take(sizeof(int32_t) * (size_t)((U + TR_CT - 1) / TR_CT));
+        w.blk_i = (int32_t*)a.take(sizeof(int32_t) * (size_t)((I + TR_CT - 1) / TR_CT));
     }
-    w.bytes = o;
+    w.bytes = a.bytes;
     return w;
 }
 
 static int tr_check_shapes(const char* fn, int64_t U, int64_t I, int dim, int n_layers, const int* widths,
-                           int seq_len, int batch, TrLayers* ly) {
-    auto fail = [&](int rc, const char* msg) {
-        set_error(std::string(fn) + ": " + msg);
-        return rc;
-    };
-    if (!(U > 0 && I > 0)) return fail(NRK_EINVAL, "empty embedding tables");
-    if (!(U <= INT32_MAX && I <= INT32_MAX)) return fail(NRK_EINVAL, "more than 2^31 - 1 table rows");
-    if (!(seq_len >= 1 && seq_len <= TR_MAXT)) return fail(NRK_EINVAL, "seq_len must be in [1, 64]");
-    if (!(batch >= 1 && batch <= TR_MAXB)) return fail(NRK_EINVAL, "batch must be in [1, 8192]");
-    if (!(dim == 16 || dim == 32 || dim == 64)) return fail(NRK_EUNSUPPORTED, "dim must be 16, 32 or 64");
-    if (!widths) return fail(NRK_EINVAL, "null widths");
-    if (n_layers < 1 || n_layers > TR_MAXL) return fail(NRK_EUNSUPPORTED, "1 to 8 hidden layers are compiled");
-    ly->n = n_layers;
-    for (int l = 0; l < n_layers; ++l) {
-        if (widths[l] < 1 || widths[l] > TR_MAXW) return fail(NRK_EUNSUPPORTED, "hidden widths must be in [1, 256]");
-        ly->w[l] = widths[l];
-    }
-    if (widths[n_layers - 1] != dim)
-        return fail(NRK_EINVAL, "last hidden width must equal the embedding dim (youtubednn_recaller.py:461-465)");
-    return NRK_OK;
+                           int seq_len, int batch, TtLayers* ly) {
+    if (!(U > 0 && I > 0)) return fail_as(fn, NRK_EINVAL, "empty embedding tables");
+    if (!(U <= INT32_MAX && I <= INT32_MAX)) return fail_as(fn, NRK_EINVAL, "more than 2^31 - 1 table rows");
+    if (!(seq_len >= 1 && seq_len <= TR_MAXT)) return fail_as(fn, NRK_EINVAL, "seq_len must be in [1, 64]");
+    if (!(batch >= 1 && batch <= TR_MAXB)) return fail_as(fn, NRK_EINVAL, "batch must be in [1, 8192]");
+    return tt_check_shape(fn, dim, n_layers, widths, ly);
 }
 
 }  // namespace nrk
@@ -735,7 +621,7 @@ extern "C" {
 size_t nrk_tt_train_workspace_bytes(int64_t n_user_rows, int64_t n_item_rows, int dim, int n_layers,
                                     const int* widths, int seq_len, int batch) {
     clear_error();
-    TrLayers ly{};
+    TtLayers ly{};
     if (tr_check_shapes(__func__, n_user_rows, n_item_rows, dim, n_layers, widths, seq_len, batch, &ly) != NRK_OK)
         return 0;
     return tr_layout(nullptr, n_user_rows, n_item_rows, dim, ly, seq_len, batch).bytes;
@@ -749,7 +635,7 @@ int nrk_tt_train_grad(const float* user_table, int64_t n_user_rows, const float*
                       int32_t* u_rows, float* u_vals, int32_t* u_count, int32_t* i_rows, float* i_vals,
                       int32_t* i_count, void* workspace, size_t workspace_bytes, nrk_stream_t stream) {
     clear_error();
-    TrLayers ly{};
+    TtLayers ly{};
     const int rc = tr_check_shapes(__func__, n_user_rows, n_item_rows, dim, n_layers, widths, seq_len, batch, &ly);
     if (rc != NRK_OK) return rc;
     NRK_REQUIRE(p >= 0.0f && p < 1.0f, "dropout p must be in [0, 1)");
@@ -769,21 +655,17 @@ int nrk_tt_train_grad(const float* user_table, int64_t n_user_rows, const float*
         in = ly.w[l];
     }
     // the weights ride in LDS when they fit beside the four waves' rows
-    const size_t wave_floats = (size_t)4 * (w.asz + 2 * TR_MAXW);
+    const size_t wave_floats = (size_t)4 * (w.asz + 2 * TT_MAXW);
     const int staged = (wave_floats + staged_floats) * sizeof(float) <= 60 * 1024;
     const size_t lds = sizeof(float) * (wave_floats + (staged ? staged_floats : 0));
     const uint32_t thr = p > 0.0f ? std::max<uint32_t>(1u, tr_threshold(p)) : 0u;
     const float scale = p > 0.0f ? 1.0f / (1.0f - p) : 1.0f;
     const int grid = (B + 3) / 4;
-#define NRK_TR_LAUNCH(DD)                                                                                     \
-    tt_train_fb_kernel<DD><<<grid, 256, lds, s>>>(user_table, item_table, weights, ly, log_off, log_items,    \
-                                                  s_user, s_pos, s_target, s_label, B, T, scale, thr, seed,   \
-                                                  (uint64_t)step, w.asz, w.dsz, staged, w.loss_b, w.act,      \
-                                                  w.delta, w.gU, w.gH, w.gT)
-    if (D == 16) NRK_TR_LAUNCH(16);
-    else if (D == 32) NRK_TR_LAUNCH(32);
-    else NRK_TR_LAUNCH(64);
-#undef NRK_TR_LAUNCH
+    tt_for_dim(D, [&](auto dc) {
+        tt_train_fb_kernel<decltype(dc)::value><<<grid, 256, lds, s>>>(
+            user_table, item_table, weights, ly, log_off, log_items, s_user, s_pos, s_target, s_label, B, T, scale, thr,
+            seed, (uint64_t)step, w.asz, w.dsz, staged, w.loss_b, w.act, w.delta, w.gU, w.gH, w.gT);
+    });
     NRK_CHECK_LAUNCH();
     tt_wgrad_kernel<<<(n_w + 63) / 64 + 1, 1024, 0, s>>>(w.act, w.delta, w.loss_b, ly, D, B, w.asz, w.dsz, n_w,
                                                         w_grad, loss);
@@ -822,8 +704,8 @@ int nrk_tt_dropout_mask(uint64_t seed, int64_t step, int layer, int batch, int w
                         nrk_stream_t stream) {
     clear_error();
     NRK_REQUIRE(batch >= 1 && batch <= TR_MAXB, "batch must be in [1, 8192]");
-    NRK_REQUIRE(width >= 1 && width <= TR_MAXW, "width must be in [1, 256]");
-    NRK_REQUIRE(layer >= 0 && layer < TR_MAXL, "layer must be in [0, 8)");
+    NRK_REQUIRE(width >= 1 && width <= TT_MAXW, "width must be in [1, 256]");
+    NRK_REQUIRE(layer >= 0 && layer < TT_MAXL, "layer must be in [0, 8)");
     NRK_REQUIRE(p >= 0.0f && p < 1.0f, "dropout p must be in [0, 1)");
     NRK_REQUIRE(step >= 0, "step must be >= 0");
     NRK_REQUIRE(out, "null pointer");
@@ -842,30 +724,21 @@ int nrk_tt_adam_step(float* weights, float* w_m, float* w_v, const float* w_grad
                      int dim, double lr, double beta1, double beta2, double eps, int64_t t,
                      nrk_stream_t stream) {
     clear_error();
-    if (!(dim == 16 || dim == 32 || dim == 64)) NRK_UNSUPPORTED("dim must be 16, 32 or 64");
+    if (const int rc = tt_check_shape(__func__, dim)) return rc;
     NRK_REQUIRE(n_weights > 0 && n_weights < ((int64_t)1 << 31), "bad n_weights");
     NRK_REQUIRE(n_user_rows > 0 && n_item_rows > 0 && n_user_rows <= INT32_MAX && n_item_rows <= INT32_MAX,
                 "bad table sizes");
-    NRK_REQUIRE(t >= 1, "t is the 1-based step number");
-    NRK_REQUIRE(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
-                "bad hyper-parameters");
+    AdamK k;
+    if (const int rc = adam_scalars(__func__, lr, beta1, beta2, eps, t, &k)) return rc;
     NRK_REQUIRE(weights && w_m && w_v && w_grad && user_table && u_m && u_v && u_rows && u_vals && u_count &&
                     item_table && i_m && i_v && i_rows && i_vals && i_count,
                 "null pointer");
-    // the scalars as _single_tensor_adam forms them, in double, then one rounding to fp32
-    const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
-    AdamK k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)std::sqrt(bc2), (float)eps,
-            (float)(-(lr / bc1))};
-    AdamSeg su{user_table, u_m, u_v, u_rows, u_vals, u_count, n_user_rows};
-    AdamSeg si{item_table, i_m, i_v, i_rows, i_vals, i_count, n_item_rows};
-    const int q = dim / 4;
-    const int wblocks = (int)((n_weights + 255) / 256);
-    const int64_t ublocks = (n_user_rows * q + 255) / 256, iblocks = (n_item_rows * q + 255) / 256;
-    NRK_REQUIRE(wblocks + ublocks + iblocks < ((int64_t)1 << 31), "tables too large for one sweep");
-    tt_adam_kernel<<<(unsigned)(wblocks + ublocks + iblocks), 256, 0, as_stream(stream)>>>(
-        weights, w_m, w_v, w_grad, n_weights, wblocks, su, si, ublocks, dim, k);
-    NRK_CHECK_LAUNCH();
-    return NRK_OK;
+    const AdamSegs<2> segs{{{user_table, u_m, u_v, u_rows, u_vals, u_count, n_user_rows},
+                            {item_table, i_m, i_v, i_rows, i_vals, i_count, n_item_rows}}};
+    const char* fn = __func__;  // inside the lambda it would name operator()
+    return tt_for_dim(dim, [&](auto dc) {
+        return adam_sweep<decltype(dc)::value>(fn, weights, w_m, w_v, w_grad, n_weights, segs, k, as_stream(stream));
+    });
 }
 
 int nrk_tt_make_samples_count(const int64_t* log_off, int64_t n_users, int64_t* pos_off, nrk_stream_t stream) {

@@ -367,20 +367,16 @@ struct UcWs {
     size_t bytes;
 };
 
-static inline size_t uc_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static UcWs uc_ws_layout(void* base, int64_t n_users, int64_t n_clicks) {
     UcWs w;
-    uint8_t* p = reinterpret_cast<uint8_t*>(base);
-    size_t o = 0;
-    auto take = [&](size_t b) { uint8_t* r = p + o; o += uc_al(b); return r; };
+    Arena a(base);
     const size_t nu = (size_t)(n_users > 0 ? n_users : 1);
     w.grid = (int)(nu < (size_t)UC_GRID ? nu : (size_t)UC_GRID);
-    w.dupf = take((size_t)(n_clicks > 0 ? n_clicks : 1));
-    w.acc = (double*)take(nu * w.grid * 8);
-    w.first = (int64_t*)take(nu * w.grid * 8);
-    w.touched = (int32_t*)take(nu * w.grid * 4);
-    w.bytes = o;
+    w.dupf = (uint8_t*)a.take((size_t)(n_clicks > 0 ? n_clicks : 1));
+    w.acc = (double*)a.take(nu * w.grid * 8);
+    w.first = (int64_t*)a.take(nu * w.grid * 8);
+    w.touched = (int32_t*)a.take(nu * w.grid * 4);
+    w.bytes = a.bytes;
     return w;
 }
 

@@ -131,6 +131,7 @@ def test_adam_step_argument_errors():
 
     assert adam(ptr=None) == _lib.NRK_EINVAL and b"null pointer" in L.nrk_last_error()
     assert adam(dim=24) == _lib.NRK_EUNSUPPORTED
+    assert adam(dim=24) == _lib.NRK_EUNSUPPORTED and b"dim must be" in L.nrk_last_error()
     assert adam(t=0) == _lib.NRK_EINVAL and b"1-based" in L.nrk_last_error()
     assert adam(lr=0.0) == _lib.NRK_EINVAL
     assert adam(n_w=0) == _lib.NRK_EINVAL
