@@ -111,8 +111,7 @@ int nrk_din_assemble(const int32_t* rec_rows, const float* rec_scores, int64_t n
                     out_item && out_hist && out_mask && out_cand && (n_ctx == 0 || out_ctx),
                 "null pointer");
     const int64_t n_pairs = nu * k_use;
-    const int64_t g = (n_pairs + 3) / 4;
-    din_assemble_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(
+    din_assemble_kernel<<<grid_for(n_pairs, 4, 65536), 256, 0, as_stream(stream)>>>(
         rec_rows, rec_scores, k_in, skip, k_use, user_feat, n_user, item_feat, n_item, user_hist, hist_len, T,
         n_ctx, ctx_bins, score_lo, score_hi, seed, u0, n_pairs, out_user, out_item, out_hist, out_ctx,
         out_mask, out_cand);
@@ -127,8 +126,7 @@ int nrk_gather_rows(const void* src, int64_t n_rows, int row_words, const int32_
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(idx && out && (src || n_rows == 0), "null pointer");
     const int64_t total = n * row_words;
-    const int64_t g = (total + 255) / 256;
-    gather_rows_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(
+    gather_rows_kernel<<<grid_for(total, 256, 65536), 256, 0, as_stream(stream)>>>(
         reinterpret_cast<const uint32_t*>(src), n_rows, row_words, idx, n, reinterpret_cast<uint32_t*>(out));
     NRK_CHECK_LAUNCH();
     return NRK_OK;

@@ -2112,8 +2112,6 @@ struct DinWs {
     size_t bytes;
 };
 
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // fast path: wave-per-sample wh + gather-on-load split-fp16 GEMM1
 static inline bool din_fast(int T, int h1) { return T <= 64 && h1 <= 256; }
 static inline bool din_fast2(int T, int h1, int h2) { return din_fast(T, h1) && h2 <= 128; }
@@ -2130,34 +2128,32 @@ static inline int din_mlp1_nt(int h1) {
 static DinWs din_ws_layout(void* base, int64_t N, int64_t S, int T, int n_user, int n_item, int n_ctx,
                            int h1, int h2) {
     DinWs w;
-    uint8_t* p = reinterpret_cast<uint8_t*>(base);
-    size_t o = 0;
+    Arena a(base);
     const int64_t n_seg = (N + S - 1) / S;
     const int64_t nb_att = n_seg * std::max<int64_t>(din_att_groups(N, S), (S + TM_SW - 1) / TM_SW);
     const int64_t nb_m = (N + 63) / 64;
     const int IN = (n_user + n_ctx + 2 * n_item) * DIN_E;
     const bool fast = din_fast(T, h1);
-    auto take = [&](size_t bytes) { uint8_t* r = p + o; o += al(bytes); return r; };
-    w.h = (float*)take((size_t)N * T * DIN_H * 4);
-    w.hpart = (double*)take((size_t)nb_att * T * DIN_H * 16);
-    w.plan = (int32_t*)take((size_t)n_seg * ((S + TM_SW - 1) / TM_SW) * TM_PLAN * 4);
-    w.hstats = (float2*)take((size_t)n_seg * T * DIN_H * 8);
-    w.mlp_in = fast ? nullptr : (float*)take((size_t)N * IN * 4);
-    w.wh = fast ? (float*)take((size_t)N * n_item * DIN_E * 4) : nullptr;
-    w.hinv = fast ? (float2*)take((size_t)n_seg * T * DIN_H * 8) : nullptr;
+    w.h = (float*)a.take((size_t)N * T * DIN_H * 4);
+    w.hpart = (double*)a.take((size_t)nb_att * T * DIN_H * 16);
+    w.plan = (int32_t*)a.take((size_t)n_seg * ((S + TM_SW - 1) / TM_SW) * TM_PLAN * 4);
+    w.hstats = (float2*)a.take((size_t)n_seg * T * DIN_H * 8);
+    w.mlp_in = fast ? nullptr : (float*)a.take((size_t)N * IN * 4);
+    w.wh = fast ? (float*)a.take((size_t)N * n_item * DIN_E * 4) : nullptr;
+    w.hinv = fast ? (float2*)a.take((size_t)n_seg * T * DIN_H * 8) : nullptr;
     // [max |wh| per segment][max |W0|][max |z1| per segment][max |W1|]
-    w.whmax = fast ? (unsigned int*)take((size_t)(2 * n_seg + 2) * 4) : nullptr;
+    w.whmax = fast ? (unsigned int*)a.take((size_t)(2 * n_seg + 2) * 4) : nullptr;
     w.w2pack = din_fast2(T, h1, h2)
-                   ? (din_half8*)take((size_t)((h1 + DIN_E - 1) / DIN_E) * din_mlp2_nt(h2) * 2048)
+                   ? (din_half8*)a.take((size_t)((h1 + DIN_E - 1) / DIN_E) * din_mlp2_nt(h2) * 2048)
                    : nullptr;
-    w.w1pack = fast ? (din_half8*)take((size_t)(IN / DIN_E) * din_mlp1_nt(h1) * 2048) : nullptr;
-    w.z1 = (float*)take((size_t)N * h1 * 4);
-    w.z1part = (double*)take((size_t)nb_m * h1 * 16);
-    w.z1stats = (float2*)take((size_t)n_seg * h1 * 8);
-    w.z2 = (float*)take((size_t)N * h2 * 4);
-    w.z2part = (double*)take((size_t)nb_m * h2 * 16);
-    w.z2stats = (float2*)take((size_t)n_seg * h2 * 8);
-    w.bytes = o;
+    w.w1pack = fast ? (din_half8*)a.take((size_t)(IN / DIN_E) * din_mlp1_nt(h1) * 2048) : nullptr;
+    w.z1 = (float*)a.take((size_t)N * h1 * 4);
+    w.z1part = (double*)a.take((size_t)nb_m * h1 * 16);
+    w.z1stats = (float2*)a.take((size_t)n_seg * h1 * 8);
+    w.z2 = (float*)a.take((size_t)N * h2 * 4);
+    w.z2part = (double*)a.take((size_t)nb_m * h2 * 16);
+    w.z2stats = (float2*)a.take((size_t)n_seg * h2 * 8);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -2187,18 +2183,6 @@ static int din_check_n_item(const char* fn, int n_item) {
     return NRK_EUNSUPPORTED;
 }
 
-// Raise a kernel's dynamic-LDS limit to the most its instantiation can ask
-// for, once per device: `done` is the launch site's function-local static,
-// one per instantiation (as launch_exact in ip_topk.hip)
-static void lds_limit_once(std::atomic<uint64_t>& done, const void* kernel, size_t bytes) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t dbit = 1ull << (dev & 63);
-    if (dev < 64 && (done.load(std::memory_order_acquire) & dbit)) return;
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    done.fetch_or(dbit, std::memory_order_release);
-}
-
 }  // namespace nrk
 
 using namespace nrk;
@@ -2220,8 +2204,7 @@ int nrk_din_remap_index(const int32_t* in, int64_t n_rows, int f_in, const int32
     NRK_REQUIRE(in && map && out, "null pointer");
     hipStream_t s = as_stream(stream);
     const int64_t n = n_rows * f_out;
-    din_remap_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 4096), 256, 0, s>>>(in, n_rows, f_in, f_out,
-                                                                                        map, out);
+    din_remap_kernel<<<grid_for(n, 256, 4096), 256, 0, s>>>(in, n_rows, f_in, f_out, map, out);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -2247,8 +2230,7 @@ int nrk_din_prepare(const float* att_w0, int n_item, const void* table, int tabl
     din_prepare_kernel<<<64, 256, 0, s>>>(att_w0, ID, pf);
     (void)hipMemsetAsync(mx, 0, 8, s);
     const int64_t n = n_table_rows * DIN_E;
-    const int64_t g = (n + 255) / 256;
-    din_absmax_kernel<<<(int)(g < 512 ? g : 512), 256, 0, s>>>(table, table_dtype, n, mx);
+    din_absmax_kernel<<<grid_for(n, 256, 512), 256, 0, s>>>(table, table_dtype, n, mx);
     din_scales_kernel<<<1, 256, 0, s>>>(pf, ID, mx, sc);
     // the position-major kernel's scales and packed weight fragments
     uint8_t* tm = reinterpret_cast<uint8_t*>(prep) + din_tm_base(n_item);
@@ -2259,7 +2241,7 @@ int nrk_din_prepare(const float* att_w0, int n_item, const void* table, int tabl
                                                                             wpack + 3 * n_item * 4 * 64);
     if (table_dtype == 1) {  // the position-major kernel reads the item rows as fp16 (bf16 tables)
         const int64_t nw = n_table_rows * DIN_E / 2;
-        din_tm_tab16_kernel<<<(unsigned)std::min<int64_t>((nw + 255) / 256, 4096), 256, 0, s>>>(
+        din_tm_tab16_kernel<<<grid_for(nw, 256, 4096), 256, 0, s>>>(
             reinterpret_cast<const uint16_t*>(table), n_table_rows * DIN_E, tsc,
             reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(prep) + din_tm_tab16_off(n_item)));
     }
@@ -2323,13 +2305,7 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
     const int G_tm = (int)((S + TM_SW - 1) / TM_SW);
     if (tm_path) {
         // persistent: one workgroup per CU (register- and LDS-bound)
-        static const int n_cu = [] {
-            int dev = 0, cu = 256;
-            if (hipGetDevice(&dev) == hipSuccess)
-                (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-            return cu > 0 ? cu : 256;
-        }();
-        const unsigned tm_grid = (unsigned)std::min<int64_t>(n_seg * G_tm, n_cu);
+        const unsigned tm_grid = grid_for(n_seg * G_tm, 1, device_cus());
         const uint8_t* pb = reinterpret_cast<const uint8_t*>(prep);
         with_rung<1, 2, 4>(n_item, [&](auto ni) {
             constexpr int NI = decltype(ni)::value;
@@ -2368,15 +2344,12 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
     if (din_fast(T, h1)) {
         // max |W0| -> packed split-fp16 W0; per-segment max |wh| (zeroed here)
         unsigned int* w1max = w.whmax + n_seg;
-        if (hipMemsetAsync(w.whmax, 0, (size_t)(2 * n_seg + 2) * 4, s) != hipSuccess) {
-            set_error("nrk_din_forward: hipMemsetAsync failed");
-            return NRK_EHIP;
-        }
+        NRK_FILL("nrk_din_forward", w.whmax, 0, (size_t)(2 * n_seg + 2) * 4, s);
         const int64_t nw = (int64_t)h1 * IN;
-        din_absmax_kernel<<<(int)std::min<int64_t>((nw + 255) / 256, 128), 256, 0, s>>>(mlp_w0, 0, nw, w1max);
+        din_absmax_kernel<<<grid_for(nw, 256, 128), 256, 0, s>>>(mlp_w0, 0, nw, w1max);
         const int NT = din_mlp1_nt(h1);
         const int64_t npk = (int64_t)(IN / DIN_E) * NT * 64;
-        const int gp = (int)std::min<int64_t>((npk + 255) / 256, 2048);
+        const unsigned gp = grid_for(npk, 256, 2048);
         with_rung<4, 8, 13, 16>(NT, [&](auto nt) {
             din_w1_pack_kernel<decltype(nt)::value><<<gp, 256, 0, s>>>(mlp_w0, h1, IN, w1max, w.w1pack);
         });
@@ -2404,7 +2377,7 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
             });
         });
     } else {
-        const int go = (int)(batch < 8192 ? batch : 8192);
+        const unsigned go = grid_for(batch, 1, 8192);
         with_table_type(table_dtype, [&](auto tt) {
             using TT = decltype(tt);
             din_att_out_kernel<TT><<<go, 256, 0, s>>>(reinterpret_cast<const TT*>(table), row_base, n_user, n_item,
@@ -2420,13 +2393,13 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
         unsigned int* z1max = w.whmax + n_seg + 1;
         unsigned int* w2max = z1max + n_seg;
         const int64_t nw = (int64_t)h2 * h1;
-        din_absmax_kernel<<<(int)std::min<int64_t>((nw + 255) / 256, 64), 256, 0, s>>>(mlp_w1, 0, nw, w2max);
+        din_absmax_kernel<<<grid_for(nw, 256, 64), 256, 0, s>>>(mlp_w1, 0, nw, w2max);
         const int NT2 = din_mlp2_nt(h2);
         const int KS2 = (h1 + DIN_E - 1) / DIN_E;
-        const int gp = (int)std::min<int64_t>(((int64_t)KS2 * NT2 * 64 + 255) / 256, 512);
+        const unsigned gp = grid_for((int64_t)KS2 * NT2 * 64, 256, 512);
         // packed W1 (KS x NT x 2 KB) + the epilogue's column sums
         auto mlp2_lds = [](int ks, int nt) { return (size_t)ks * nt * 2048 + (size_t)4 * nt * 16 * 16; };
-        const unsigned g2 = (unsigned)std::min<int64_t>((batch + MLP1_ROWS - 1) / MLP1_ROWS, 512);
+        const unsigned g2 = grid_for(batch, MLP1_ROWS, 512);
         with_rung<2, 4, 5, 8>(NT2, [&](auto nt) {
             constexpr int NTV = decltype(nt)::value;
             din_w1_pack_kernel<NTV><<<gp, 256, 0, s>>>(mlp_w1, h2, h1, w2max, w.w2pack);
@@ -2442,7 +2415,7 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
     }
     col_stats_kernel<<<dim3(gs, (h2 + 3) / 4), 256, 0, s>>>(w.z2part, bps, (int)nb_m, h2, batch, S,
                                                             nullptr, w.z2stats);
-    din_head_kernel<<<(unsigned)std::min<int64_t>((batch + 15) / 16, 8192), 256, 0, s>>>(
+    din_head_kernel<<<grid_for(batch, 16, 8192), 256, 0, s>>>(
         w.z2, w.z2stats, batch, S, h2, mlp_w2, mlp_b2, out_probs, out_logits);
     NRK_CHECK_LAUNCH();
     return NRK_OK;

@@ -843,8 +843,7 @@ static int dt_run(const DtShape& s, const DtWs& w, const DtIdx& ix, const float*
                   float* wg, int32_t* rows, float* vals, int32_t* count, hipStream_t st) {
     const DtOff o = dt_offsets(s);
     const int B = s.B, T = s.T, Di = s.Di, IN = s.IN, H1 = s.H1, H2 = s.H2, C = T * 36, WS = Di + 1;
-    const int ew = 2048;  // blocks of the grid-stride elementwise kernels
-    auto eg = [&](int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, ew); };
+    auto eg = [](int64_t n) { return grid_for(n, 256, 2048); };  // the grid-stride elementwise kernels
     // ---- forward
     const size_t lds_fwd = sizeof(float) * (36 * WS + Di + 36) + sizeof(int) * T * NI;
     dt_att_fwd_kernel<NI><<<B, 256, lds_fwd, st>>>(ix, wts + o.aw0, wts + o.ab0, w.z);
@@ -924,7 +923,7 @@ static int dt_run(const DtShape& s, const DtWs& w, const DtIdx& ix, const float*
     }
     dt_emb_starts_kernel<<<eg(N), 256, 0, st>>>(w.keys2, w.flag, w.seg, N, w.starts, rows, count);
     DtSrc src{w.dx0, w.dk, IN, s.S, s.Fu + s.Fc + NI, T, NI};
-    const int pg = (int)std::min<int64_t>((N + 7) / 8, 8192);
+    const unsigned pg = grid_for(N, 8, 8192);
     dt_emb_piece_kernel<<<pg, 256, 0, st>>>(w.cid2, w.seg, w.starts, N, src, vals, w.epart);
     dt_emb_long_kernel<<<pg, 256, 0, st>>>(w.starts, count, w.epart, vals);
     NRK_CHECK_LAUNCH();

@@ -104,8 +104,10 @@ int nrk_row_normalize(const float* x, int64_t n, int dim, float* out, float* nor
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(x && out, "null pointer");
     const size_t lds = sizeof(float) * 64 * (size_t)(dim | 1);
-    (void)hipFuncSetAttribute((const void*)row_normalize_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    constexpr size_t lds_max = sizeof(float) * 64 * (256 | 1);  // dim <= 256: 65,792 bytes
+    static_assert(lds_max <= CU_LDS_BYTES, "row_normalize_kernel LDS");
+    static std::atomic<uint64_t> lds_set{0};
+    lds_limit_once(lds_set, (const void*)row_normalize_kernel, lds_max);
     row_normalize_kernel<<<(unsigned)((n + 63) / 64), 64, lds, as_stream(stream)>>>(x, n, dim, out,
                                                                                  norms);
     NRK_CHECK_LAUNCH();

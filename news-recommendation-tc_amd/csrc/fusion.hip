@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void fuse_kernel(
 
 // Users with more than FUSE_MAX entries (nrk_fuse_wide): the same per-entry
 // arithmetic in the same order, one wave per user with every array in
-// dynamic LDS (nw = next_pow2(max entries) slots), the leaders ranked by an
+// dynamic LDS (nw = pow2_at_least(max entries, 64) slots), the leaders ranked by an
 // LDS bitonic sort on (merged desc, first occurrence asc).
 __global__ __launch_bounds__(64) void fuse_wide_kernel(
     const int64_t* __restrict__ offsets, int64_t n_users, const int32_t* __restrict__ item,
@@ -395,12 +395,16 @@ int nrk_fuse_wide(const int64_t* offsets, int64_t n_users, const int32_t* item, 
                 "null pointer");
     NRK_REQUIRE(norm != 2 || (zmean && zstd), "z-score needs zmean / zstd");
     NRK_REQUIRE((seen_off == nullptr) == (seen == nullptr), "seen_off and seen go together");
-    int nw = 64;
-    while (nw < max_entries) nw <<= 1;
-    const size_t lds = (size_t)nw * (sizeof(Cand) + 2 * sizeof(double) + 3 * sizeof(int32_t));
-    (void)hipFuncSetAttribute((const void*)fuse_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // per slot: a Cand, two doubles, three int32; at most FUSE_WMAX slots (90,112 bytes)
+    constexpr size_t slot = sizeof(Cand) + 2 * sizeof(double) + 3 * sizeof(int32_t);
+    constexpr size_t lds_max = pow2_at_least(FUSE_WMAX, 64) * slot;
+    static_assert(lds_max <= CU_LDS_BYTES, "fuse_wide_kernel LDS");
+    const int nw = pow2_at_least(max_entries, 64);
+    const size_t lds = (size_t)nw * slot;
+    static std::atomic<uint64_t> lds_set{0};
+    lds_limit_once(lds_set, (const void*)fuse_wide_kernel, lds_max);
     FuseParams p{strategy, norm, n_methods, topk, gmin, gmax};
-    fuse_wide_kernel<<<(int)(n_users < 65536 ? n_users : 65536), 64, lds, as_stream(stream)>>>(
+    fuse_wide_kernel<<<grid_for(n_users, 1, 65536), 64, lds, as_stream(stream)>>>(
         offsets, n_users, item, score, method, rank, weight, zmean, zstd, seen_off, seen, p, nw, out_item,
         out_score, out_cnt);
     NRK_CHECK_LAUNCH();

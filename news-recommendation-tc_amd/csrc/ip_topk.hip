@@ -2606,7 +2606,7 @@ __global__ __launch_bounds__(256) void ip_exact_kernel(
 // One workgroup per listed user: the k-th largest exact key by an 8-bit
 // radix select over the whole catalog (8 histogram passes), then the items
 // above it plus the first ties in row order (k winners in all), ordered by
-// an LDS bitonic sort of ns = next_pow2(max(k, 64)) entries (dynamic LDS).
+// an LDS bitonic sort of ns = pow2_at_least(k, 64) entries (dynamic LDS).
 __global__ __launch_bounds__(256) void ip_fallback_kernel(
     const float* __restrict__ users, const float* __restrict__ items, int64_t n_items, int dim,
     int k, int ns, int64_t row_offset, const int32_t* __restrict__ ovf_list,
@@ -3074,8 +3074,6 @@ struct IpWs {
     size_t bytes;
 };
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // band entries kept per user (k + the entries within 2 eps of theta)
 static inline int ip_bandcap(int k) {
     const int b = ((2 * k + 32 + 31) / 32) * 32;
@@ -3111,48 +3109,20 @@ static IpWs ip_ws_layout(void* base, int64_t n_users, int64_t n_items, int k, in
     w.m2 = ip_m2(n_items, k, dim);
     w.blk_lo = 0;
     w.blk_hi = (int)n_blocks_of(n_items);
-    uint8_t* p = reinterpret_cast<uint8_t*>(base);
-    size_t off = 0;
-    w.ovf_count = reinterpret_cast<int32_t*>(p + off);
-    off += 256;
-    w.ucut = reinterpret_cast<float2*>(p + off);
-    off += align256((size_t)n_users * sizeof(float2));
-    w.cnt = reinterpret_cast<int32_t*>(p + off);
-    off += align256((size_t)n_users * sizeof(int32_t));
-    w.ovf_flag = reinterpret_cast<int32_t*>(p + off);
-    off += align256((size_t)n_users * sizeof(int32_t));
-    w.ovf_list = reinterpret_cast<int32_t*>(p + off);
-    off += align256((size_t)n_users * sizeof(int32_t));
-    w.uinfo = reinterpret_cast<float4*>(p + off);
-    off += align256((size_t)n_users * sizeof(float4));
-    w.acnt = reinterpret_cast<int32_t*>(p + off);
-    off += align256((size_t)n_users * 2 * sizeof(int32_t));
-    w.cand = reinterpret_cast<uint2*>(p + off);
-    off += align256((size_t)n_users * w.bandcap * sizeof(uint2));
-    w.app = reinterpret_cast<uint2*>(p + off);
-    off += align256((size_t)n_users * 2 * (size_t)w.m2 * sizeof(uint2));
-    w.fbk = reinterpret_cast<uint32_t*>(p + off);
-    off += align256((size_t)std::min<int64_t>(n_users, FB_GRID) * (size_t)n_items * sizeof(uint32_t));
-    w.slow_list = reinterpret_cast<int32_t*>(p + off);
-    off += align256((size_t)n_users * sizeof(int32_t));
-    w.bytes = off;
+    Arena a(base);
+    w.ovf_count = (int32_t*)a.take(256);
+    w.ucut = (float2*)a.take((size_t)n_users * sizeof(float2));
+    w.cnt = (int32_t*)a.take((size_t)n_users * sizeof(int32_t));
+    w.ovf_flag = (int32_t*)a.take((size_t)n_users * sizeof(int32_t));
+    w.ovf_list = (int32_t*)a.take((size_t)n_users * sizeof(int32_t));
+    w.uinfo = (float4*)a.take((size_t)n_users * sizeof(float4));
+    w.acnt = (int32_t*)a.take((size_t)n_users * 2 * sizeof(int32_t));
+    w.cand = (uint2*)a.take((size_t)n_users * w.bandcap * sizeof(uint2));
+    w.app = (uint2*)a.take((size_t)n_users * 2 * (size_t)w.m2 * sizeof(uint2));
+    w.fbk = (uint32_t*)a.take((size_t)std::min<int64_t>(n_users, FB_GRID) * (size_t)n_items * sizeof(uint32_t));
+    w.slow_list = (int32_t*)a.take((size_t)n_users * sizeof(int32_t));
+    w.bytes = a.bytes;
     return w;
-}
-
-static inline int next_pow2(int x) {
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-// compute units of the current device (the persistent grids)
-static int n_cus() {
-    static const int n_cu = [] {
-        int dev = 0, cu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-        return cu > 0 ? cu : 256;
-    }();
-    return n_cu;
 }
 
 // The tile range of one scan launch and its list pre-pass: up to 64 tiles
@@ -3265,7 +3235,7 @@ static inline bool shard_listbound(int k) { return (k + 1) / 2 <= 32; }
 
 // persistent grid of the shard kernels: SH_WG_PER_CU 4-wave workgroups per CU
 static int sh_grid(int64_t n_users) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n_users + 3) / 4, (int64_t)n_cus() * SH_WG_PER_CU));
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n_users + 3) / 4, (int64_t)device_cus() * SH_WG_PER_CU));
 }
 
 // empty shard range: no appends, uinfo.z = 0 (shard_band: no band, no cut)
@@ -3282,20 +3252,14 @@ __global__ void ip_empty_range_kernel(int64_t n_users, int32_t* __restrict__ acn
 static void launch_exact(const float* users, int64_t n_users, const float* items, int64_t n_items, int dim, int k,
                          int64_t row_offset, const IpWs& w, float* out_s, int32_t* out_r, double* out_e,
                          hipStream_t s) {
-    const int ns = next_pow2(std::max(k, 64));
+    const int ns = pow2_at_least(k, 64);
     const size_t lds = (size_t)ns * sizeof(Cand);
-    // the dynamic-LDS limit of both kernels, raised once per device to the
-    // largest k's sort (it was set again on every finish)
-    static std::atomic<uint64_t> attr_done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t dbit = 1ull << (dev & 63);
-    if (dev >= 64 || !(attr_done.load(std::memory_order_acquire) & dbit)) {
-        const int lds_max = next_pow2(IP_KMAX) * (int)sizeof(Cand);
-        (void)hipFuncSetAttribute((const void*)ip_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        (void)hipFuncSetAttribute((const void*)ip_fallback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        attr_done.fetch_or(dbit, std::memory_order_release);
-    }
+    // the dynamic-LDS limit of both kernels: the largest k's sort
+    constexpr size_t lds_max = pow2_at_least(IP_KMAX) * sizeof(Cand);
+    static_assert(lds_max <= CU_LDS_BYTES, "ip_exact / ip_fallback LDS");
+    static std::atomic<uint64_t> exact_set{0}, fallback_set{0};
+    lds_limit_once(exact_set, (const void*)ip_exact_kernel, lds_max);
+    lds_limit_once(fallback_set, (const void*)ip_fallback_kernel, lds_max);
     const int grid = (int)std::min<int64_t>(n_users, FB_GRID);
     ip_exact_kernel<<<grid, 256, lds, s>>>(users, items, n_items, dim, k, ns, row_offset, w.ovf_list, w.ovf_count,
                                            out_s, out_r, out_e, w.fbk, w.slow_list, w.ovf_count + 1);
@@ -3311,7 +3275,7 @@ static void with_sort_width(int total, F&& fn) {
     if (total <= 64) fn(std::integral_constant<int, 1>{}, 64);
     else if (total <= 128) fn(std::integral_constant<int, 2>{}, 128);
     else if (total <= 256) fn(std::integral_constant<int, 4>{}, 256);
-    else fn(std::integral_constant<int, 0>{}, next_pow2(total));
+    else fn(std::integral_constant<int, 0>{}, pow2_at_least(total));
 }
 template <int E>
 static size_t sort_lds_bytes(int ns) {
@@ -3389,20 +3353,17 @@ int nrk_ip_catalog_build(const float* items, int64_t n_items, int dim, void* cat
     hipStream_t s = as_stream(stream);
     const size_t body = catalog_body_bytes(n_items, dp);
     CatalogHdr* hdr = reinterpret_cast<CatalogHdr*>(reinterpret_cast<uint8_t*>(catalog) + body);
-    if (hipMemsetAsync(hdr, 0, CATALOG_HDR, s) != hipSuccess) {
-        set_error("nrk_ip_catalog_build: hipMemsetAsync failed");
-        return NRK_EHIP;
-    }
+    NRK_FILL(__func__, hdr, 0, CATALOG_HDR, s);
     const int64_t total = n_blocks_of(n_items) * (dp / 16) * 64;
     if (total > 0) {
-        const int g2 = (int)std::min<int64_t>((n_items + 15) / 16, 2048);  // >= one row group per wave
+        const unsigned g2 = grid_for(n_items, 16, 2048);  // >= one row group per wave
         catalog_norm_kernel<<<g2, 256, 0, s>>>(items, n_items, dim, hdr);
     }
     catalog_hdr_kernel<<<1, 1, 0, s>>>(hdr, dim, dp);
     if (total > 0) {
-        const int g2 = (int)std::min<int64_t>((n_items + 15) / 16, 2048);
+        const unsigned g2 = grid_for(n_items, 16, 2048);
         catalog_dnorm_kernel<<<g2, 256, 0, s>>>(items, n_items, dim, hdr);
-        const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
+        const unsigned grid = grid_for(total, 256, 8192);
         catalog_pack_kernel<<<grid, 256, 0, s>>>(items, n_items, dim, dp, hdr,
                                                  reinterpret_cast<uint4*>(catalog));
         if (catalog_has_hb(dp))
@@ -3455,18 +3416,15 @@ static int screen_phases(const float* users, int64_t n_users, const void* catalo
         scan_dispatch(users, (int)n_users, cat, (int)n_items, dim, k, w, s);
     }
     if (phases & 2) {
-        if (hipMemsetAsync(w.ovf_count, 0, 256, s) != hipSuccess) {
-            set_error("nrk_ip_topk_screen: hipMemsetAsync failed");
-            return NRK_EHIP;
-        }
+        NRK_FILL("nrk_ip_topk_screen", w.ovf_count, 0, 256, s);
         if (n_items == 0) {
             // nothing to search: every output row is padding
             (void)hipMemsetAsync(w.cnt, 0, (size_t)n_users * sizeof(int32_t), s);
             (void)hipMemsetAsync(w.ovf_flag, 0, (size_t)n_users * sizeof(int32_t), s);
             (void)hipMemsetAsync(w.ucut, 0xFF, (size_t)n_users * sizeof(float2), s);  // NaN cut: no band
         } else if (k > IP_KFAST) {
-            const int grid = (int)std::min<int64_t>((n_users + 255) / 256, 4096);
-            ip_all_exact_kernel<<<grid, 256, 0, s>>>(n_users, w.cnt, w.ovf_flag, w.ovf_list, w.ovf_count);
+            ip_all_exact_kernel<<<grid_for(n_users, 256, 4096), 256, 0, s>>>(n_users, w.cnt, w.ovf_flag, w.ovf_list,
+                                                                             w.ovf_count);
         } else {
             ip_select_kernel<<<sh_grid(n_users), 256, 0, s>>>(n_users, k, w.m2, w.bandcap, w.app, w.acnt, w.uinfo,
                                                               w.cand, w.cnt, w.ucut, w.ovf_flag, w.ovf_list,
@@ -3605,8 +3563,7 @@ int nrk_ip_topk_shard_screen(const float* users, int64_t n_users, const void* ca
         w.bnd_m = m;
     }
     if (blk_lo == blk_hi || n_items == 0) {
-        ip_empty_range_kernel<<<(int)std::min<int64_t>((n_users + 255) / 256, 4096), 256, 0, s>>>(n_users, w.acnt,
-                                                                                               w.uinfo);
+        ip_empty_range_kernel<<<grid_for(n_users, 256, 4096), 256, 0, s>>>(n_users, w.acnt, w.uinfo);
         if (lbnd &&
             hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_bound), 0xFF800000u /* -inf */,
                               (size_t)n_users * m, s) != hipSuccess) {
@@ -3657,11 +3614,8 @@ int nrk_ip_topk_refine_x(const float* users, int64_t n_users, const float* items
     if (k > IP_KFAST) NRK_UNSUPPORTED("the band refine needs k <= 128 (larger k: exact path, ovf_in = 1)");
     const IpWs w = ip_ws_layout(workspace, n_users, n_items, k, dim);
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(w.ovf_count, 0, 256, s) != hipSuccess) {
-        set_error("nrk_ip_topk_refine_x: hipMemsetAsync failed");
-        return NRK_EHIP;
-    }
-    ip_ovf_collect_kernel<<<(int)std::min<int64_t>((n_users + 255) / 256, 4096), 256, 0, s>>>(
+    NRK_FILL(__func__, w.ovf_count, 0, 256, s);
+    ip_ovf_collect_kernel<<<grid_for(n_users, 256, 4096), 256, 0, s>>>(
         n_users, ovf_in, w.ovf_flag, w.ovf_list, w.ovf_count);
     const uint8_t* cat = reinterpret_cast<const uint8_t*>(catalog);
     launch_refine(users, n_users, items, cat, n_items, dim, k, row_offset,

@@ -1571,7 +1571,7 @@ __global__ __launch_bounds__(1024) void cf_topn_heavy_kernel(const int64_t* __re
 // The reference has no limit on itemcf_sim_item_topk / the recall topk
 // (itemcf_recaller.py:41-54, :125) or on rank_and_recommend's topk.  Above
 // the 64-lane register paths: one wave per row keeps a running top-K
-// (K = next_pow2(k)) best-first in LDS; each chunk of up to K new entries
+// (K = pow2_at_least(k, 64)) best-first in LDS; each chunk of up to K new entries
 // lands behind it and the 2K are re-sorted by an LDS bitonic sort on
 // (score desc, first asc) -- a total order, so the result does not depend on
 // the chunking.
@@ -1706,38 +1706,24 @@ struct CfWs {
     size_t bytes;
 };
 
-static inline size_t cf_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// 256-byte-aligned bump allocation over a workspace (a null base: sizes only)
-struct CfBump {
-    uint8_t* p;
-    size_t o;
-    template <class T>
-    T* take(size_t bytes) {
-        T* r = reinterpret_cast<T*>(p + o);
-        o += cf_al(bytes);
-        return r;
-    }
-};
-
 static CfWs cf_ws_layout(void* base, int64_t P) {
     CfWs w;
-    CfBump a{reinterpret_cast<uint8_t*>(base), 0};
+    Arena a(base);
     const size_t n = (size_t)(P > 0 ? P : 1);
     const size_t nblk = (n + RS_TILE - 1) / RS_TILE;
-    w.ka = a.take<uint64_t>(n * 8);
-    w.kb = a.take<uint64_t>(n * 8);
-    w.va = a.take<int32_t>(n * 4);
-    w.vb = a.take<int32_t>(n * 4);
-    w.w = a.take<double>(n * 8);
-    w.counts = a.take<uint32_t>(256 * nblk * 4);
-    w.totals = a.take<uint32_t>(256 * 4);
-    w.blkcnt = a.take<uint32_t>(nblk * 4);
-    w.blkoff = a.take<uint32_t>(nblk * 4);
-    w.tail = a.take<double>(nblk * 8);
-    w.carry = a.take<double>(nblk * 8);
-    w.brk = a.take<int32_t>(nblk * 4);
-    w.bytes = a.o;
+    w.ka = (uint64_t*)a.take(n * 8);
+    w.kb = (uint64_t*)a.take(n * 8);
+    w.va = (int32_t*)a.take(n * 4);
+    w.vb = (int32_t*)a.take(n * 4);
+    w.w = (double*)a.take(n * 8);
+    w.counts = (uint32_t*)a.take(256 * nblk * 4);
+    w.totals = (uint32_t*)a.take(256 * 4);
+    w.blkcnt = (uint32_t*)a.take(nblk * 4);
+    w.blkoff = (uint32_t*)a.take(nblk * 4);
+    w.tail = (double*)a.take(nblk * 8);
+    w.carry = (double*)a.take(nblk * 8);
+    w.brk = (int32_t*)a.take(nblk * 4);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -1755,17 +1741,17 @@ struct RcWs {
 static RcWs rc_ws_layout(void* base, int64_t n_cand) {
     RcWs w;
     w.sort = cf_ws_layout(base, n_cand);
-    CfBump a{reinterpret_cast<uint8_t*>(base), w.sort.bytes};
+    Arena a(base, w.sort.bytes);
     const size_t n = (size_t)(n_cand > 0 ? n_cand : 1);
-    w.eq = a.take<int32_t>(n * 4);
-    w.ej = a.take<int32_t>(n * 4);
-    w.ev = a.take<double>(n * 8);
-    w.ef = a.take<int64_t>(n * 8);
-    w.n_emit = a.take<int64_t>(8);
-    w.hlist = a.take<int2>((n / RC_CAP + 1) * sizeof(int2));  // at most n / (RC_CAP + 1) overflow queries
-    w.hcnt = a.take<int32_t>(16);                              // + the overflow candidate total at +8
-    w.htot = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(w.hcnt) + 8);
-    w.bytes = a.o;
+    w.eq = (int32_t*)a.take(n * 4);
+    w.ej = (int32_t*)a.take(n * 4);
+    w.ev = (double*)a.take(n * 8);
+    w.ef = (int64_t*)a.take(n * 8);
+    w.n_emit = (int64_t*)a.take(8);
+    w.hlist = (int2*)a.take((n / RC_CAP + 1) * sizeof(int2));  // at most n / (RC_CAP + 1) overflow queries
+    w.hcnt = (int32_t*)a.take(16);                              // + the overflow candidate total at +8
+    w.htot = w.hcnt ? reinterpret_cast<unsigned long long*>(w.hcnt + 2) : nullptr;
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -1775,11 +1761,11 @@ static int bits_for(int64_t n) {  // smallest b with 2^b > n
     return b;
 }
 
-static inline int cf_wide_k(int k) {
-    int p = 64;
-    while (p < k) p <<= 1;
-    return p;
-}
+// The wide top-k kernels (cf_topn_wide, rc_topk_wide; k > 64): two lists of
+// K = pow2_at_least(k, 64) entries in dynamic LDS, k <= CF_WIDE_MAX
+static inline size_t cf_wide_lds(int K) { return (size_t)2 * K * sizeof(CfEnt); }
+constexpr size_t CF_WIDE_LDS_MAX = (size_t)2 * pow2_at_least(CF_WIDE_MAX, 64) * sizeof(CfEnt);  // 98,304
+static_assert(RC_TOPK_MAX <= CF_WIDE_MAX && CF_WIDE_LDS_MAX <= CU_LDS_BYTES, "wide top-k LDS");
 
 // The sort keys: (i << bj | j) over nbits bits, and the all-ones sentinel of
 // the entries that are dropped (i == j; an item of the query's own history).
@@ -1804,8 +1790,6 @@ static inline CfParams cf_params(double loc_alpha, double loc_alpha_rev, double 
     return CfParams{loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha, cf_dt_zero(time_alpha),
                     cf_ln(time_alpha), cf_ln(created_alpha)};
 }
-
-static inline int cf_grid(int64_t blocks, int64_t cap = 65536) { return (int)(blocks < cap ? blocks : cap); }
 
 // The stable radix sort of n > 0 (key, slot) pairs over nbits key bits, then
 // one (i, j, sum, first slot) entry per distinct key other than the sentinel,
@@ -1879,7 +1863,7 @@ int nrk_itemcf_sim(const int64_t* offsets, int64_t n_users, const int32_t* items
     (void)hipMemsetAsync(out_cnt, 0, sizeof(int64_t) * (size_t)n_items, s);
     const CfParams prm = cf_params(loc_alpha, loc_alpha_rev, loc_beta, time_alpha, created_alpha);
     if (n_users > 0 && n_pairs > 0)
-        cf_pairs_flat_kernel<<<cf_grid((n_pairs + 4 * CF_CHUNK - 1) / (4 * CF_CHUNK), 8192), 256, 0, s>>>(
+        cf_pairs_flat_kernel<<<grid_for(n_pairs, 4 * CF_CHUNK, 8192), 256, 0, s>>>(
             offsets, n_users, items, ts, created, pair_off, 0, prm, k.bj, k.sentinel, w.ka, w.va, w.w);
     if (n_users > 0)
         cf_item_count_kernel<<<1024, CF_CNT_THREADS, 0, s>>>(offsets, n_users, items,
@@ -1904,18 +1888,17 @@ int nrk_itemcf_topn(const int64_t* row_off, int64_t n_rows, const int32_t* cols,
     // cols / vals / first may be null when the CSR has no entries (empty torch tensors)
     NRK_REQUIRE(row_off && out_cols && out_vals && out_cnt, "null pointer");
     if (topn > 64) {
-        const int K = cf_wide_k(topn);
-        const size_t lds = (size_t)2 * K * sizeof(CfEnt);
-        (void)hipFuncSetAttribute((const void*)cf_topn_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        cf_topn_wide_kernel<<<cf_grid(n_rows), 64, lds, as_stream(stream)>>>(
+        const int K = pow2_at_least(topn, 64);
+        static std::atomic<uint64_t> lds_set{0};
+        lds_limit_once(lds_set, (const void*)cf_topn_wide_kernel, CF_WIDE_LDS_MAX);
+        cf_topn_wide_kernel<<<grid_for(n_rows, 1, 65536), 64, cf_wide_lds(K), as_stream(stream)>>>(
             row_off, n_rows, cols, vals, first, topn, K, out_cols, out_vals, out_cnt);
         NRK_CHECK_LAUNCH();
         return NRK_OK;
     }
-    cf_topn_kernel<<<cf_grid((n_rows + 3) / 4), 256, 0, as_stream(stream)>>>(
+    cf_topn_kernel<<<grid_for(n_rows, 4, 65536), 256, 0, as_stream(stream)>>>(
         row_off, n_rows, cols, vals, first, topn, out_cols, out_vals, out_cnt);
-    cf_topn_heavy_kernel<<<cf_grid((n_rows + 1023) / 1024, 512), 1024, 0, as_stream(stream)>>>(
+    cf_topn_heavy_kernel<<<grid_for(n_rows, 1024, 512), 1024, 0, as_stream(stream)>>>(
         row_off, n_rows, cols, vals, first, topn, out_cols, out_vals, out_cnt);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -1930,7 +1913,7 @@ int nrk_itemcf_recall_offsets(const int64_t* q_slot, int64_t n_query, const int6
     hipStream_t s = as_stream(stream);
     if (n_query > 0) {
         NRK_REQUIRE(q_slot && offsets && items && nbr_cnt, "null pointer");
-        rc_count_kernel<<<cf_grid((n_query + 3) / 4), 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cnt, cand_off);
+        rc_count_kernel<<<grid_for(n_query, 4, 65536), 256, 0, s>>>(q_slot, n_query, offsets, items, nbr_cnt, cand_off);
     }
     scan_exclusive_kernel<ScanVals><<<1, 1024, 0, s>>>(ScanVals{cand_off}, n_query, cand_off);
     NRK_CHECK_LAUNCH();
@@ -1968,7 +1951,7 @@ int nrk_itemcf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
         NRK_UNSUPPORTED("n_query * n_items too large for 64-bit keys");
     const RcParams prm{loc_beta, created_alpha, cf_ln(created_alpha), topn, ke, bk.bj};
     if (n_cand > 0)
-        rc_cand_kernel<<<cf_grid((n_query + 3) / 4), 256, 0, s>>>(
+        rc_cand_kernel<<<grid_for(n_query, 4, 65536), 256, 0, s>>>(
             q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, created, emb_cols, emb_vals, emb_cnt, prm,
             cand_off, bk.sentinel, bk.keys, bk.slots, bk.contrib);
     return rc_back_finish(q_slot, n_query, offsets, items, n_items, hot, n_hot, cand_off, n_cand, topk, out_items,
@@ -2001,7 +1984,6 @@ int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offset
                    hipStream_t s) {
     const RcWs w = rc_ws_layout(workspace, n_cand);
     const CfKeys k = rc_keys(n_items, n_query);
-    const int64_t g = (n_query + 3) / 4;
     const int64_t n = n_cand;
     // topk <= 64: every query with <= RC_CAP candidates is finished by
     // rc_query_kernel from rc_cand's output; the radix path then runs over
@@ -2009,25 +1991,16 @@ int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offset
     // buffers (device-side count: its launches exit at once when there are
     // none).  topk > 64: every query takes the radix path.
     const bool fused = topk <= 64;
-    int gl = cf_grid(g);  // rc_topk's grid: every query, or the listed ones
+    unsigned gl = grid_for(n_query, 4, 65536);  // rc_topk's grid: every query, or the listed ones
     if (n > 0) {
         const int64_t* n_dev = nullptr;
         if (fused) {
             (void)hipMemsetAsync(w.hcnt, 0, 16, s);
-            static const int qgrid = [] {
-                int dev = 0, cu = 256, per = 0;
-                if (hipGetDevice(&dev) == hipSuccess)
-                    (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)rc_query_kernel, 256, 0) !=
-                        hipSuccess ||
-                    per <= 0)
-                    per = 4;
-                return per * (cu > 0 ? cu : 256);
-            }();
-            rc_query_kernel<<<cf_grid(g, qgrid), 256, 0, s>>>(
+            static const int64_t qgrid = resident_blocks((const void*)rc_query_kernel, 256, 0);
+            rc_query_kernel<<<grid_for(n_query, 4, qgrid), 256, 0, s>>>(
                 q_slot, n_query, offsets, items, cand_off, w.sort.ka, w.sort.w, k.sentinel, k.bj, hot, n_hot, topk,
                 out_items, out_scores, out_src, out_cnt, w.hlist, w.hcnt, w.htot);
-            gl = cf_grid((n / (RC_CAP + 1) + 4) / 4);
+            gl = (unsigned)std::min<int64_t>((n / (RC_CAP + 1) + 4) / 4, 65536);
             rc_compact_kernel<<<gl, 256, 0, s>>>(cand_off, w.sort.ka, w.sort.va, w.hlist, w.hcnt, w.sort.kb,
                                                  w.sort.vb);
             n_dev = reinterpret_cast<const int64_t*>(w.htot);
@@ -2045,13 +2018,12 @@ int rc_back_finish(const int64_t* q_slot, int64_t n_query, const int64_t* offset
                                           w.n_emit, topk, out_items, out_scores, out_src, out_cnt,
                                           listed ? w.hlist : nullptr, listed ? w.hcnt : nullptr);
     } else {
-        const int K = cf_wide_k(topk);
-        const size_t lds = (size_t)2 * K * sizeof(CfEnt);
-        (void)hipFuncSetAttribute((const void*)rc_topk_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        rc_topk_wide_kernel<<<cf_grid(n_query), 64, lds, s>>>(q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej,
-                                                              w.ev, w.ef, w.n_emit, topk, K, out_items, out_scores,
-                                                              out_src, out_cnt);
+        const int K = pow2_at_least(topk, 64);
+        static std::atomic<uint64_t> lds_set{0};
+        lds_limit_once(lds_set, (const void*)rc_topk_wide_kernel, CF_WIDE_LDS_MAX);
+        rc_topk_wide_kernel<<<grid_for(n_query, 1, 65536), 64, cf_wide_lds(K), s>>>(
+            q_slot, n_query, offsets, items, hot, n_hot, w.eq, w.ej, w.ev, w.ef, w.n_emit, topk, K, out_items,
+            out_scores, out_src, out_cnt);
     }
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -2065,7 +2037,7 @@ int nrk_itemcf_row_offsets(const int32_t* ei, int64_t n, int64_t n_rows, int64_t
     clear_error();
     NRK_REQUIRE(n >= 0 && n_rows >= 0, "negative size");
     NRK_REQUIRE(row_off && (n == 0 || ei), "null pointer");
-    cf_row_offsets_kernel<<<cf_grid((n_rows + 1 + 255) / 256), 256, 0, as_stream(stream)>>>(ei, n, n_rows, row_off);
+    cf_row_offsets_kernel<<<grid_for(n_rows + 1, 256, 65536), 256, 0, as_stream(stream)>>>(ei, n, n_rows, row_off);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
 }
@@ -2113,7 +2085,7 @@ int nrk_itemcf_reduce(const uint64_t* keys, const int32_t* slots, const double* 
     NRK_REQUIRE(keys && slots && w && item_cnt && out_i && out_j && out_v && out_first, "null pointer");
     const CfWs ws = cf_ws_layout(workspace, n);
     NRK_REQUIRE(workspace_bytes >= ws.bytes, "workspace too small");
-    cf_iota_copy_kernel<<<cf_grid((n + 255) / 256), 256, 0, s>>>(keys, n, ws.ka, ws.va);
+    cf_iota_copy_kernel<<<grid_for(n, 256, 65536), 256, 0, s>>>(keys, n, ws.ka, ws.va);
     cf_sort_reduce(ws, false, n, cf_sim_keys(n_items), w, reinterpret_cast<const unsigned long long*>(item_cnt), slots,
                    nullptr, out_i, out_j, out_v, out_first, out_n, s);
     NRK_CHECK_LAUNCH();

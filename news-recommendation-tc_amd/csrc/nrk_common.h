@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <cstdio>
 #include <string>
 #include <type_traits>
@@ -54,14 +55,71 @@ inline hipStream_t as_stream(nrk_stream_t s) { return reinterpret_cast<hipStream
 // counts the same.
 struct Arena {
     char* base;
-    size_t bytes = 0;
-    explicit Arena(void* b) : base(static_cast<char*>(b)) {}
+    size_t bytes;
+    // `from`: go on after the pieces another layout carved from the same base
+    explicit Arena(void* b, size_t from = 0) : base(static_cast<char*>(b)), bytes(from) {}
     void* take(size_t n) {
         void* r = base ? base + bytes : nullptr;
         bytes += (n + 255) & ~(size_t)255;
         return r;
     }
 };
+
+// -------------------------------------------------------- launch helpers --
+// Host only: what every entry point needs around its <<<...>>>.
+
+// min(ceil(n / per_block), cap) workgroups
+inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
+    const int64_t g = (n + per_block - 1) / per_block;
+    return (unsigned)(g < cap ? g : cap);
+}
+
+// the power of two >= max(x, floor); floor is a power of two
+constexpr int pow2_at_least(int x, int floor = 1) {
+    int p = floor;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+// compute units of the current device (the persistent grids), asked once per
+// process; 256 when the query fails
+inline int device_cus() {
+    static const int n_cu = [] {
+        int dev = 0, cu = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
+        return cu > 0 ? cu : 256;
+    }();
+    return n_cu;
+}
+
+// workgroups of `fn` (threads, lds bytes of dynamic LDS) the device holds at once
+inline int64_t resident_blocks(const void* fn, int threads, size_t lds) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess || per_cu <= 0)
+        per_cu = 4;
+    return (int64_t)per_cu * device_cus();
+}
+
+// Raise a kernel's dynamic-LDS limit to `bytes`, the most any admissible call
+// can ask for, once per device: `done` is the launch site's function-local
+// static, one per kernel instantiation.  Devices past the 64 bits set it on
+// every call.
+inline void lds_limit_once(std::atomic<uint64_t>& done, const void* kernel, size_t bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t dbit = 1ull << (dev & 63);
+    if (dev < 64 && (done.load(std::memory_order_acquire) & dbit)) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done.fetch_or(dbit, std::memory_order_release);
+}
+constexpr size_t CU_LDS_BYTES = 163840;  // a CU's 160 KB: the ceiling of every lds_limit_once
+
+// hipMemsetAsync, or the error of entry point `fn` and NRK_EHIP
+#define NRK_FILL(fn, ptr, value, bytes, stream)                                              \
+    do {                                                                                     \
+        if (hipMemsetAsync((ptr), (value), (bytes), (stream)) != hipSuccess)                 \
+            return ::nrk::fail_as((fn), NRK_EHIP, "hipMemsetAsync failed");                  \
+    } while (0)
 
 constexpr int WAVE = 64;
 

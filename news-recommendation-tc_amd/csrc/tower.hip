@@ -268,14 +268,20 @@ __global__ __launch_bounds__(256) void tt_item_kernel(const float* __restrict__ 
 
 using namespace nrk;
 
-// workgroups of 256 threads resident at once on the device (occupancy API x
-// CUs), at most one per 4 users
+// workgroups of 256 threads resident at once on the device, at most one per 4 users
 static int tt_grid(const void* fn, size_t lds, int64_t n) {
-    int per_cu = 0, dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)per_cu * std::max(cus, 1)));
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, resident_blocks(fn, 256, lds)));
 }
+
+// tt_user_kernel's dynamic LDS: both layers' padded weights and biases, then
+// the four waves' rows.  It grows with h0, so h0 = 128 (the entry point's
+// limit) is an instantiation's most: 106,240 bytes at dim 64
+constexpr size_t tt_user_lds(int dim, int h0, int h1) {
+    const size_t h0p = (size_t)((h0 + 3) & ~3), h1p = (size_t)((h1 + 3) & ~3);
+    return sizeof(float) *
+           ((size_t)h0 * (2 * dim + 4) + h0p + (size_t)h1 * (h0p + 4) + h1p + (size_t)4 * (2 * dim + 128));
+}
+constexpr int TT_H0_MAX = 128;
 
 extern "C" {
 
@@ -288,22 +294,22 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
     NRK_REQUIRE(n >= 0 && seq_len >= 1 && seq_len <= 64, "bad sizes (seq_len must be in [1, 64])");
     NRK_REQUIRE(n_user_rows > 0 && n_item_rows > 0, "empty embedding tables");
     if (const int rc = tt_check_shape(__func__, dim)) return rc;
-    NRK_REQUIRE(h0 >= 1 && h0 <= 128, "h0 must be in [1, 128]");
+    NRK_REQUIRE(h0 >= 1 && h0 <= TT_H0_MAX, "h0 must be in [1, 128]");
     NRK_REQUIRE(h1 == dim, TT_LAST_WIDTH);
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(user_table && item_table && uid && hist && hist_len && w0 && b0 && w1 && b1 && out,
                 "null pointer");
-    const size_t h0p = (size_t)((h0 + 3) & ~3), h1p = (size_t)((h1 + 3) & ~3);
-    const size_t lds = sizeof(float) * ((size_t)h0 * (2 * dim + 4) + h0p + (size_t)h1 * (h0p + 4) + h1p +
-                                        (size_t)4 * (2 * dim + 128));
+    const size_t lds = tt_user_lds(dim, h0, h1);
     hipStream_t s = as_stream(stream);
     // persistent grid of resident workgroups only (the weights' LDS admits ~5
     // per CU): a grid larger than the resident set left the queued
     // workgroups to run after the first ones finished, on a thinner machine
     tt_for_dim(dim, [&](auto dc) {
         constexpr int DD = decltype(dc)::value;
-        (void)hipFuncSetAttribute((const void*)tt_user_kernel<DD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
+        constexpr size_t lds_max = tt_user_lds(DD, TT_H0_MAX, DD);  // h1 == dim
+        static_assert(lds_max <= CU_LDS_BYTES, "tt_user_kernel LDS");
+        static std::atomic<uint64_t> lds_set{0};
+        lds_limit_once(lds_set, (const void*)tt_user_kernel<DD>, lds_max);
         const int grid = tt_grid((const void*)tt_user_kernel<DD>, lds, n);
         tt_user_kernel<DD><<<grid, 256, lds, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, w0, b0, h0,
                                                   w1, b1, h1, out);
@@ -324,7 +330,7 @@ int nrk_tt_user_fwd_layers(const float* user_table, int64_t n_user_rows, const f
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(user_table && item_table && uid && hist && hist_len && weights && out, "null pointer");
     hipStream_t s = as_stream(stream);
-    const int grid = (int)std::min<int64_t>((n + 3) / 4, 2048);
+    const unsigned grid = grid_for(n, 4, 2048);
     tt_for_dim(dim, [&](auto dc) {
         tt_user_mlp_kernel<decltype(dc)::value><<<grid, 256, 0, s>>>(user_table, item_table, uid, hist, hist_len, n,
                                                                      seq_len, weights, ly, out);
@@ -341,7 +347,7 @@ int nrk_tt_item_fwd(const float* item_table, int64_t n_item_rows, int dim, const
     if (n == 0) return NRK_OK;
     NRK_REQUIRE(item_table && ids && out, "null pointer");
     hipStream_t s = as_stream(stream);
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+    const unsigned grid = grid_for(n, 256, 4096);
     tt_for_dim(dim, [&](auto dc) { tt_item_kernel<decltype(dc)::value><<<grid, 256, 0, s>>>(item_table, ids, n, out); });
     NRK_CHECK_LAUNCH();
     return NRK_OK;

@@ -673,12 +673,7 @@ int nrk_tt_train_grad(const float* user_table, int64_t n_user_rows, const float*
     const bool one = w.n_chunks == 1;
     TrTable tu{one ? u_rows : w.crow_u, one ? u_vals : w.cval_u, one ? u_count : w.ccnt_u, w.CS};
     TrTable ti{one ? i_rows : w.crow_i, one ? i_vals : w.cval_i, one ? i_count : w.ccnt_i, w.cap_i};
-    if (!one) {
-        if (hipMemsetAsync(w.mark_u, 0, w.mark_bytes, s) != hipSuccess) {
-            set_error(std::string(__func__) + ": hipMemsetAsync failed");
-            return NRK_EHIP;
-        }
-    }
+    if (!one) NRK_FILL(__func__, w.mark_u, 0, w.mark_bytes, s);
     tt_emb_sort_kernel<<<dim3(w.n_chunks, 2), 1024, (size_t)TR_KEYS * 6, s>>>(
         log_off, log_items, s_user, s_pos, s_target, B, T, w.CS, D, w.gU, w.gH, w.gT, tu, ti);
     NRK_CHECK_LAUNCH();
@@ -692,7 +687,7 @@ int nrk_tt_train_grad(const float* user_table, int64_t n_user_rows, const float*
                                                   u_rows, u_count, i_rows, i_count);
         NRK_CHECK_LAUNCH();
         const int64_t most = (int64_t)B * (T + 1) * D;
-        const int mg = (int)std::min<int64_t>((most + 255) / 256, 4096);
+        const unsigned mg = grid_for(most, 256, 4096);
         tt_emb_merge_kernel<<<dim3(mg, 2), 256, 0, s>>>(tu, ti, w.n_chunks, D, u_rows, u_count, u_vals, i_rows,
                                                         i_count, i_vals);
         NRK_CHECK_LAUNCH();
@@ -711,7 +706,7 @@ int nrk_tt_dropout_mask(uint64_t seed, int64_t step, int layer, int batch, int w
     NRK_REQUIRE(out, "null pointer");
     const uint32_t thr = p > 0.0f ? std::max<uint32_t>(1u, tr_threshold(p)) : 0u;
     const int64_t n = (int64_t)batch * width;
-    tt_dropout_mask_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 2048), 256, 0, as_stream(stream)>>>(
+    tt_dropout_mask_kernel<<<grid_for(n, 256, 2048), 256, 0, as_stream(stream)>>>(
         seed, (uint64_t)step, layer, batch, width, thr, out);
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -762,7 +757,7 @@ int nrk_tt_make_samples(const int64_t* log_off, const int32_t* log_items, int64_
     NRK_REQUIRE(log_off && log_items && pos_off && s_user && s_pos && s_target && s_label && (negsample == 0 || pool),
                 "null pointer");
     const int64_t n = n_pos * (1 + negsample);
-    tt_make_samples_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 8192), 256, 0, as_stream(stream)>>>(
+    tt_make_samples_kernel<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(
         log_off, log_items, n_users, pos_off, n_pos, negsample, pool, n_pool, seed, s_user, s_pos, s_target, s_label);
     NRK_CHECK_LAUNCH();
     return NRK_OK;

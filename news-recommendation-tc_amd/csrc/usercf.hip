@@ -417,9 +417,8 @@ int nrk_usercf_topn(const int64_t* i_off, int32_t n_items, const int32_t* i_user
     NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
     hipStream_t s = as_stream(stream);
     if (n_clicks > 0) {
-        const int64_t g = (n_clicks + 255) / 256;
-        uc_dup_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, s>>>(i_off, n_items, i_users, u_off, u_items, n_clicks,
-                                                                 w.dupf);
+        uc_dup_kernel<<<grid_for(n_clicks, 256, 4096), 256, 0, s>>>(i_off, n_items, i_users, u_off, u_items, n_clicks,
+                                                                    w.dupf);
     }
     uc_rows_kernel<false><<<w.grid, UC_THREADS, 0, s>>>(i_off, i_users, u_off, u_items, act, pen, w.dupf, n_users,
                                                         w.acc, w.first, w.touched, topn, uc_sel_k(topn), out_cols,
@@ -442,9 +441,8 @@ int nrk_usercf_sim(const int64_t* i_off, int32_t n_items, const int32_t* i_users
     NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
     hipStream_t s = as_stream(stream);
     if (n_clicks > 0) {
-        const int64_t g = (n_clicks + 255) / 256;
-        uc_dup_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, s>>>(i_off, n_items, i_users, u_off, u_items, n_clicks,
-                                                                 w.dupf);
+        uc_dup_kernel<<<grid_for(n_clicks, 256, 4096), 256, 0, s>>>(i_off, n_items, i_users, u_off, u_items, n_clicks,
+                                                                    w.dupf);
     }
     uc_rows_kernel<true><<<w.grid, UC_THREADS, 0, s>>>(i_off, i_users, u_off, u_items, act, pen, w.dupf, n_users,
                                                        w.acc, w.first, w.touched, 1, UC_THREADS, nullptr, nullptr,
@@ -463,9 +461,8 @@ int nrk_usercf_recall_offsets(const int64_t* q_slot, int64_t n_query, const int6
     hipStream_t s = as_stream(stream);
     if (n_query > 0) {
         NRK_REQUIRE(q_slot && offsets && nbr_cols && nbr_cnt, "null pointer");
-        const int64_t g = (n_query + 3) / 4;
-        uc_count_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, s>>>(q_slot, n_query, offsets, nbr_cols, nbr_cnt,
-                                                                     topn, cand_off);
+        uc_count_kernel<<<grid_for(n_query, 4, 65536), 256, 0, s>>>(q_slot, n_query, offsets, nbr_cols, nbr_cnt, topn,
+                                                                    cand_off);
     }
     rc_scan_exclusive(cand_off, n_query, s);
     NRK_CHECK_LAUNCH();
@@ -502,12 +499,10 @@ int nrk_usercf_recall(const int64_t* q_slot, int64_t n_query, const int64_t* off
     if (!rc_back_buffers(workspace, n_query, n_items, n_cand, &bk))
         NRK_UNSUPPORTED("n_query * n_items too large for 64-bit keys");
     const UcParams prm{created_alpha, cf_ln(created_alpha), topn, ke, bk.bj};
-    if (n_cand > 0) {
-        const int64_t g = (n_query + 3) / 4;
-        uc_cand_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, s>>>(
+    if (n_cand > 0)
+        uc_cand_kernel<<<grid_for(n_query, 4, 65536), 256, 0, s>>>(
             q_slot, n_query, offsets, items, nbr_cols, nbr_vals, nbr_cnt, loc_w, created, emb_cols, emb_vals,
             emb_cnt, prm, cand_off, bk.sentinel, bk.keys, bk.slots, bk.contrib);
-    }
     return rc_back_finish(q_slot, n_query, offsets, items, n_items, hot, n_hot, cand_off, n_cand, topk, out_items,
                           out_scores, out_src, out_cnt, workspace, s);
 }
