@@ -173,16 +173,24 @@ int nrk_ip_topk(const float* users, int64_t n_users, const float* items, const v
                 nrk_stream_t stream);
 
 /* The two phases of nrk_ip_topk, for callers that pipeline or time them:
- * screen (fp16 MFMA scan -> per-user candidate band in the workspace) and
- * finish (exact fp64 rescoring + ordering, exact fallback for overflowed
- * users).  finish must follow screen on the same workspace.  finish reads
- * the packed catalog (may be NULL) for an fp16 prefilter of the candidate
- * band before the exact fp32-row rescoring. */
+ * screen (fp16 MFMA scan -> per user two append lists of half-block maxima,
+ * their list bound and eps in the workspace; per-user (cut, eps) reads
+ * (-inf, eps) after it) and finish (exact fp64 rescoring + ordering, exact
+ * fallback for overflowed users).  finish must follow screen on the same
+ * workspace, once.  After a plain screen, finish compacts the candidate band
+ * from the append lists itself (every entry >= list bound - 2 eps); after
+ * nrk_ip_topk_bound it reads the band that call built.  finish reads the
+ * packed catalog (may be NULL) for an fp16 prefilter of the candidate band
+ * before the exact fp32-row rescoring. */
 int nrk_ip_topk_screen(const float* users, int64_t n_users, const void* catalog, int64_t n_items,
                        int dim, int k, void* workspace, size_t workspace_bytes,
                        nrk_stream_t stream);
-/* nrk_ip_topk_screen in its two launches (timing / profiling of the MFMA
- * scan alone): nrk_ip_topk_scan, then nrk_ip_topk_select, same arguments. */
+/* nrk_ip_topk_screen in its two parts (timing / profiling of the MFMA scan
+ * alone): nrk_ip_topk_scan, then nrk_ip_topk_select, same arguments.
+ * nrk_ip_topk_select clears the workspace header (overflow counts, "no band
+ * built") and, where there is no scan (no items, k > 128), marks the users;
+ * it launches no kernel otherwise: the per-user select (theta, the k-th
+ * largest appended maximum, and its band) runs in nrk_ip_topk_bound only. */
 int nrk_ip_topk_scan(const float* users, int64_t n_users, const void* catalog, int64_t n_items, int dim, int k,
                      void* workspace, size_t workspace_bytes, nrk_stream_t stream);
 int nrk_ip_topk_select(const float* users, int64_t n_users, const void* catalog, int64_t n_items, int dim, int k,
@@ -195,8 +203,10 @@ int nrk_ip_topk_finish(const float* users, int64_t n_users, const float* items,
 
 /* Catalog-sharded runs, between screen and
  * finish:
- *   nrk_ip_topk_bound (same k as the screen) writes, per user, the m
- *   (<= 256) largest exact lower
+ *   nrk_ip_topk_bound (same k as the screen) builds the band of the user's
+ *   append lists (every entry >= theta - 2 eps, theta = the k-th largest
+ *   appended maximum; finish then reads this band and its cut instead of the
+ *   lists) and writes, per user, the m (<= 256) largest exact lower
  *   bounds this shard's screen found, descending, fp32 [n_users, m], -inf
  *   padded: each one bounds a distinct item's exact score from below.
  *   After an all_gather of every shard's [n_users, m] block (layout

@@ -65,6 +65,7 @@ __host__ __device__ constexpr int scan_tb(int dp) {
 constexpr int IP_SEL = 512;     // appended maxima >= theta_lb held by the select
 constexpr int IP_BQ = 288;      // largest band (k = 128); the refine holds SV + 32 entries
 constexpr int IP_KRING = 256;   // prefilter-kept rows awaiting an exact round (ring, power of two)
+constexpr int WS_BAND_BUILT = 2;  // workspace header word: a band was built since the screen (see IpWs)
 constexpr size_t CATALOG_HDR = 256;
 
 __host__ __device__ static inline int pad_dim(int d) {
@@ -586,7 +587,7 @@ template <int DP, int NW, int NSL, int UG, int MT>
 __global__ __launch_bounds__(NW * 64, 2) void ip_scan_kernel(
     const float* __restrict__ users, int n_users, const uint8_t* __restrict__ catalog, int n_items, int dim, int k,
     int m2, uint2* __restrict__ app, int32_t* __restrict__ acnt, float4* __restrict__ uinfo, int tile_lo,
-    int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m) {
+    int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m, float2* __restrict__ ucut) {
     constexpr int DS = DP / 16;
     constexpr int BLOCK_BYTES = 64 * DP;
     constexpr int TB = scan_tb(DP);
@@ -627,7 +628,10 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_scan_kernel(
         eps_s[g] = eps * scl;
         // the user's record now (its list bound .x at the end): scl and eps
         // are not held through the scan
-        if (h == 0 && user < n_users) uinfo[user] = make_float4(-INFINITY, eps_s[g], scl, eps);
+        if (h == 0 && user < n_users) {
+            uinfo[user] = make_float4(-INFINITY, eps_s[g], scl, eps);
+            ucut[user] = make_float2(-INFINITY, eps);  // no cut yet; eps where callers read it
+        }
         tau[g] = live[g] ? -FLT_MAX : INFINITY;
 #pragma unroll
         for (int i = 0; i < MT; ++i) t[g][i] = (live[g] && i >= MT - 1 - jk) ? -INFINITY : INFINITY;
@@ -1039,7 +1043,7 @@ template <int DP, int NSL, int MT>
 __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kernel(
     const float* __restrict__ users, int n_users, const uint8_t* __restrict__ catalog, int n_items, int dim, int k,
     int m2, uint2* __restrict__ app, int32_t* __restrict__ acnt, float4* __restrict__ uinfo, int tile_lo,
-    int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m, int insp) {
+    int tile_hi, int n_pre, int pstride, float* __restrict__ bnd, int bnd_m, int insp, float2* __restrict__ ucut) {
     constexpr int NPW = 4, UG = 8, NB = SCAN_WS_NB, UGB = UG / NB, DS = DP / 16;
     constexpr int BLOCK_BYTES = 64 * DP;
     constexpr int TB = scan_tb(DP);
@@ -1365,7 +1369,10 @@ __global__ __launch_bounds__(64 * 4 * (1 + SCAN_WS_NB), 1) void ip_scan_ws_kerne
         const int user = ubase + (gb + g) * 32 + q;
         scan_user_setup<DS>(users, n_users, dim, user, h, vmax, dvmax, sv_scale, uf, eps, scl, live[g]);
         eps_s[g] = eps * scl;
-        if (h == 0 && user < n_users) uinfo[user] = make_float4(-INFINITY, eps_s[g], scl, eps);
+        if (h == 0 && user < n_users) {
+            uinfo[user] = make_float4(-INFINITY, eps_s[g], scl, eps);
+            ucut[user] = make_float2(-INFINITY, eps);  // no cut yet; eps where callers read it
+        }
         tau[g] = live[g] ? -FLT_MAX : INFINITY;
 #pragma unroll
         for (int i = 0; i < MT; ++i) t[g][i] = (live[g] && i >= MT - 1 - jk) ? -INFINITY : INFINITY;
@@ -1783,6 +1790,7 @@ __global__ __launch_bounds__(256) void ip_select_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nw = (int64_t)gridDim.x * 4;
     const unsigned long long lt = (1ull << lane) - 1ull;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ovf_count[WS_BAND_BUILT] = 1;  // the finish reads this band
     // persistent waves (see the shard kernels): the next user's counts and
     // record load during this one; entries load SH_ENT x 64 at a time (the
     // user's entries: list 0 [0, a0), then list 1 [0, a1))
@@ -1873,7 +1881,10 @@ __global__ void ip_all_exact_kernel(int64_t n_users, int32_t* __restrict__ cand_
         ovf_flag[u] = 1;
         ovf_list[u] = (int32_t)u;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *ovf_count = (int32_t)n_users;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *ovf_count = (int32_t)n_users;
+        ovf_count[WS_BAND_BUILT] = 1;
+    }
 }
 
 // ------------------------------------------------------------ refinement --
@@ -1947,6 +1958,18 @@ __device__ __forceinline__ int ring_push(int32_t* ring, int kc, int lane, bool k
 // 128, and finish went 0.871 -> 0.776 ms at 4 / 0.772 at 6 waves per SIMD
 // (one box, two runs each)
 constexpr int REFINE_WPE = 6;
+// List mode's first window: entries of each append list loaded with the
+// per-user state, before the list lengths are known.  Config 2: 85.1 entries
+// per list on average, 99th percentile 114, 0.06% of the lists above 128 (98%
+// above 64), the longest 151 (tools/band_stats.py)
+constexpr int REFINE_LW = 128;
+// One more user for the exact path.  ovf_list has n_users slots: a finish
+// repeated on one screen lists its users again, and must not run past them
+__device__ __forceinline__ void ovf_push(int32_t* __restrict__ ovf_list, int32_t* __restrict__ ovf_count,
+                                         int64_t n_users, int64_t u) {
+    const int p = atomicAdd(ovf_count, 1);
+    if (p < n_users) ovf_list[p] = (int32_t)u;
+}
 // FK: out_e == nullptr, so up to 64 survivors are sorted on one u64 key: the
 // final order taken on the fp32 score (with the exact sort behind it whenever
 // two fp32 scores tie)
@@ -1956,15 +1979,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
     const uint8_t* __restrict__ catalog, int64_t n_items, int dim, int k, int64_t row_offset,
     const uint2* __restrict__ cand, int bandcap, const int32_t* __restrict__ cand_cnt,
     const float2* __restrict__ ucut, const int32_t* __restrict__ ovf_flag, int32_t* __restrict__ ovf_list,
-    int32_t* __restrict__ ovf_count, float* __restrict__ out_s, int32_t* __restrict__ out_r,
-    double* __restrict__ out_e, int n_src = 0,
+    int32_t* __restrict__ ovf_count, const int32_t* __restrict__ band_built, const uint2* __restrict__ app, int m2,
+    const int32_t* __restrict__ acnt, const float4* __restrict__ uinfo, float* __restrict__ out_s,
+    int32_t* __restrict__ out_r, double* __restrict__ out_e, int n_src = 0,
     int64_t src_users = 0, int x_cap = 0, const int32_t* __restrict__ src_cnt = nullptr) {
     constexpr int SE = SV / WAVE;
     __shared__ Cand surv[4][SV];
     __shared__ int32_t krow[4][IP_KRING];
     constexpr int RS = DS4 + 1;  // staged row stride in float4 (one float4 of padding)
     __shared__ float4 stage[DS4 > 0 ? 4 : 1][DS4 > 0 ? 32 * RS : 1];  // half a round (32 rows) at a time
-    __shared__ uint32_t bandq[4][SV + 32 > IP_BQ ? SV + 32 : IP_BQ];
+    constexpr int BQN = SV + 32 > IP_BQ ? SV + 32 : IP_BQ;
+    __shared__ uint32_t bandq[4][BQN];
     __shared__ __attribute__((aligned(16))) float ushl[4][DS4 > 0 ? 1 : 256];  // DS4 == 0: the user's fp16 values
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t u = (int64_t)blockIdx.x * 4 + wave;
@@ -1973,13 +1998,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
     // count and cut, the user's row and (select slots) the first 32 band
     // entries are loaded together before anything branches on them
     const bool slots = n_src == 0;  // kernel argument: uniform
+    // List mode (no band was built since the screen: *band_built == 0, a
+    // wave-uniform scalar, branched on once): the band is compacted below from
+    // the scan's two append lists at the cut lb - 2 eps of the scan's own list
+    // bound lb (uinfo.x <= theta, reached by 2 (jk + 1) >= k half-blocks: the
+    // same screen guarantee as the select's theta - 2 eps; a band of up to 64
+    // entries is then cut down to the select's own, see phase 1).  The first
+    // REFINE_LW entries of each list load with the rest of the state (indices
+    // clamped to the list's m2 >= 64 slots).
+    const bool lists = slots && *band_built == 0;
     const float* uv = users + u * dim;
-    const int32_t ovf_u = ovf_flag[u];
-    const int nbd_slots = slots ? cand_cnt[u] : 0;
-    const float2 ce = ucut[u];
     const float uv_r = uv[lane < dim ? lane : 0];  // unconditional (a branch around a load serialises the batch)
-    // first 32 band slots (lanes 32-63 re-read slot 0: same line, no traffic)
-    const uint2 ent0 = slots ? cand[(size_t)u * bandcap + (lane < 32 ? lane : 0)] : make_uint2(0u, 0u);
+    int32_t ovf_u = 0;
+    int nbd_slots = 0;
+    float2 ce = make_float2(-INFINITY, 0.0f);
+    float cut_s = -INFINITY;  // list mode: the cut in the scan's scaled units
+    float eps_sc = 0.0f, scl = 1.0f;  // list mode: the scan's scaled eps and its power-of-two scale
+    int2 ac = make_int2(0, 0);
+    constexpr int LWN = REFINE_LW / WAVE;
+    uint2 lw[2][LWN] = {};  // [0][0]: the first band slots otherwise
+    if (lists) {
+        const uint2* l0 = app + (size_t)(2 * u) * m2;
+        ac = reinterpret_cast<const int2*>(acnt)[u];
+        const float4 ui = uinfo[u];
+#pragma unroll
+        for (int w = 0; w < 2; ++w)
+#pragma unroll
+            for (int j = 0; j < LWN; ++j) lw[w][j] = l0[(size_t)w * m2 + min(j * WAVE + lane, m2 - 1)];
+        // acnt counts the entries offered, not the m2 stored: decided before
+        // any read past the first window
+        if (ac.x > m2 || ac.y > m2) {
+            if (lane == 0) ovf_push(ovf_list, ovf_count, n_users, u);
+            return;
+        }
+        eps_sc = ui.y;
+        scl = ui.z;
+        if (ui.x != -INFINITY) {
+            cut_s = round_down_sub(ui.x, 2.0f * ui.y);
+            ce = make_float2(cut_s / ui.z, ui.w);
+        } else {
+            ce.y = ui.w;
+        }
+    } else {
+        ovf_u = ovf_flag[u];
+        nbd_slots = slots ? cand_cnt[u] : 0;
+        ce = ucut[u];
+        // first 32 band slots (lanes 32-63 re-read slot 0: same line, no traffic)
+        if (slots) lw[0][0] = cand[(size_t)u * bandcap + (lane < 32 ? lane : 0)];
+    }
+    const uint2 ent0 = lw[0][0];
     if (ovf_u) return;
     // band: per-user slots of the select (n_src == 0), or the fixed-slot
     // exchange of the catalog-sharded owner protocol (n_src > 0): source s's
@@ -1997,7 +2064,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
     }
     if (nsrc_tot > IP_BQ) {
         // more than the LDS holds: exact path
-        if ((threadIdx.x & 63) == 0) ovf_list[atomicAdd(ovf_count, 1)] = (int32_t)u;
+        if (lane == 0) ovf_push(ovf_list, ovf_count, n_users, u);
         return;
     }
     // zero user: every score is exactly 0 -> the lowest rows win the ties
@@ -2019,11 +2086,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
     }
     const int nbd = n_src > 0 ? 0 : nbd_slots;
     const uint2* bd = cand + (size_t)u * bandcap;
+    auto cut_thr = [](float cx, float eps) {  // cut + eps, rounded down: what a survivor's exact score reaches
+        const double t = (double)cx + (double)eps;
+        return t - fabs(t) * 1e-15 - 1e-300;
+    };
     double thr = -INFINITY;
-    if (ce.x != -INFINITY) {
-        thr = (double)ce.x + (double)ce.y;
-        thr = thr - fabs(thr) * 1e-15 - 1e-300;  // round down
-    }
+    if (ce.x != -INFINITY) thr = cut_thr(ce.x, ce.y);
     // The cut in the screen's scaled fp16 units (exact power-of-two rescale):
     // |fp16 score - exact| <= eps, so every item with exact >= cut + eps has
     // an fp16 score >= cut.  Used twice: (a) band entries (half-blocks) whose
@@ -2035,11 +2103,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
     // for the exact score.
     constexpr int DSK = DS4 / 4;  // 16-dim k-steps of the packed layout
     const bool pre = catalog != nullptr && ce.x != -INFINITY;
+    // list mode has the cut in scaled units already (no catalog header), and
+    // filters its lists with it whether or not there is a packed catalog
+    const bool bcut = lists ? ce.x != -INFINITY : pre;
     // the user's fp16 values, read 8 at a time by the prefilter (wave-uniform:
     // in registers they held 4 DS4 / 2 VGPRs for the whole kernel)
     __shared__ __attribute__((aligned(16))) _Float16 ushs[4][DS4 > 0 ? 4 * DS4 : 8];
     _Float16* ush = ushs[wave];
-    float pcut = 0.0f;
+    float pcut = cut_s;
     if (pre) {
         const int dpc = pad_dim(dim);
         const int64_t nblk_c = (n_items + 31) >> 5;
@@ -2053,14 +2124,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
             for (int d = lane; d < 4 * DS4; d += WAVE) ush[d] = (_Float16)(uv[d] * su);
             wave_sync_lds();
         }
-        pcut = ce.x * (su * hdr->scale);
+        if (!lists) pcut = ce.x * (su * hdr->scale);
     }
     // ---- 1. band compaction into LDS (list order kept; sources in rank order)
     int nband = 0;
     auto take_one = [&](uint2 ent, int e, int cnt) {
-        const bool kp = e < cnt && (!pre || __uint_as_float(ent.x) >= pcut);
+        const bool kp = e < cnt && (!bcut || __uint_as_float(ent.x) >= pcut);
         const unsigned long long bal = __ballot(kp);
-        if (kp) bandq[wave][nband + __popcll(bal & ((1ull << lane) - 1ull))] = ent.y;
+        const int pos = nband + __popcll(bal & ((1ull << lane) - 1ull));
+        if (kp && pos < BQN) bandq[wave][pos] = ent.y;  // the select's band fits; a list's may not
+        // list mode: the first 64 maxima as keys beside their ids (theta below; krow is free until phase 2)
+        if (lists && kp && pos < WAVE) krow[wave][pos] = (int32_t)fkey(__uint_as_float(ent.x));
         nband += __popcll(bal);
     };
     auto take = [&](const uint2* __restrict__ src, int cnt) {
@@ -2086,6 +2160,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
                 if (e < c2) bandq[wave][nband + e] = src[e];
                 nband += min(WAVE, c2 - b0);
             }
+        }
+    } else if (lists) {
+        // list 0 [0, a0), then list 1 [0, a1): the order the select wrote
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            const int a = w ? ac.y : ac.x;
+            const uint2* src = app + (size_t)(2 * u + w) * m2;
+#pragma unroll
+            for (int j = 0; j < LWN; ++j)
+                if (j * WAVE < a) take_one(lw[w][j], j * WAVE + lane, a);
+            for (int b0 = REFINE_LW; b0 < a; b0 += WAVE) {  // a <= m2 here
+                const int e = b0 + lane;
+                take_one(e < a ? src[e] : make_uint2(0u, 0u), e, a);
+            }
+        }
+        if (nband > BQN) {  // more than the LDS holds: exact path
+            if (lane == 0) ovf_push(ovf_list, ovf_count, n_users, u);
+            return;
+        }
+        // The band at lb - 2 eps holds every appended maximum >= lb, at least
+        // k of them, so its k-th largest IS the select's theta: up to 64
+        // entries (nearly every user) take one wave sort, and the band shrinks
+        // to the select's own, theta - 2 eps (config 2: 38.6 -> 32.2
+        // half-blocks per user, each a 1-KB prefilter gather).  A longer band
+        // keeps the list cut.
+        if (bcut && nband <= WAVE && nband >= k) {
+            const float theta = fkey_inv(lds_select(reinterpret_cast<uint32_t*>(krow[wave]), nband, k - 1, lane));
+            const float cut2 = round_down_sub(theta, 2.0f * eps_sc);
+            const uint32_t key = lane < nband ? (uint32_t)krow[wave][lane] : 0u;
+            const uint32_t id = bandq[wave][lane < nband ? lane : 0];
+            const bool kp = lane < nband && fkey_inv(key) >= cut2;
+            const unsigned long long bal = __ballot(kp);
+            wave_sync_lds();  // every id is read before its slot is rewritten
+            if (kp) bandq[wave][__popcll(bal & ((1ull << lane) - 1ull))] = id;
+            nband = __popcll(bal);
+            pcut = cut2;
+            thr = cut_thr(cut2 / scl, ce.y);
         }
     } else {
         take(bd, nbd);
@@ -2414,7 +2525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DS4 == 16 ?
         while (kc > ko) exact_generic(kc - ko < WAVE ? kc - ko : WAVE);
     }
     if (cnt > SV) {  // dense exact ties: hand the user to the exact fallback
-        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1)] = (int32_t)u;
+        if (lane == 0) ovf_push(ovf_list, ovf_count, n_users, u);
         return;
     }
     wave_sync_lds();
@@ -2497,14 +2608,15 @@ __global__ __launch_bounds__(256) void ip_exact_kernel(
     const float* __restrict__ users, const float* __restrict__ items, int64_t n_items, int dim, int k, int ns,
     int64_t row_offset, const int32_t* __restrict__ ovf_list, const int32_t* __restrict__ ovf_count,
     float* __restrict__ out_s, int32_t* __restrict__ out_r, double* __restrict__ out_e,
-    uint32_t* __restrict__ scratch, int32_t* __restrict__ slow_list, int32_t* __restrict__ slow_count) {
+    uint32_t* __restrict__ scratch, int32_t* __restrict__ slow_list, int32_t* __restrict__ slow_count,
+    int list_cap) {
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
     Cand* sel = reinterpret_cast<Cand*>(dyn);
     __shared__ unsigned int hist[2048];
     __shared__ unsigned int part[256];
     __shared__ int s_bin, s_krem, s_eq, sel_n;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int cnt = *ovf_count;
+    const int cnt = min(*ovf_count, list_cap);  // the list's slots (see ovf_push)
     const int kk = (int)(n_items < k ? n_items : k);
     uint32_t* key = scratch + (size_t)blockIdx.x * n_items;
     for (int qi = blockIdx.x; qi < cnt; qi += gridDim.x) {
@@ -2611,7 +2723,7 @@ __global__ __launch_bounds__(256) void ip_fallback_kernel(
     const float* __restrict__ users, const float* __restrict__ items, int64_t n_items, int dim,
     int k, int ns, int64_t row_offset, const int32_t* __restrict__ ovf_list,
     const int32_t* __restrict__ ovf_count, float* __restrict__ out_s, int32_t* __restrict__ out_r,
-    double* __restrict__ out_e) {
+    double* __restrict__ out_e, int list_cap) {
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
     Cand* sel = reinterpret_cast<Cand*>(dyn);
     __shared__ unsigned int hist[256];
@@ -2620,7 +2732,7 @@ __global__ __launch_bounds__(256) void ip_fallback_kernel(
     __shared__ int s_krem;
     __shared__ int wcnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cnt = *ovf_count;
+    const int cnt = min(*ovf_count, list_cap);  // the list's slots (see ovf_push)
     const int kk = (int)(n_items < k ? n_items : k);
     for (int qi = blockIdx.x; qi < cnt; qi += gridDim.x) {
         const int64_t u = ovf_list[qi];
@@ -3055,6 +3167,11 @@ __global__ void ip_ovf_collect_kernel(int64_t n_users, const int32_t* __restrict
 // [hdr 256 B: ovf_count] [ucut f2] [cand_cnt] [ovf_flag] [ovf_list] [uinfo f4]
 // [acnt 2 per user] [cand: bandcap per user] [app: 2 x m2 per user]
 // ucut .. acnt depend on n_users only (nrk_ip_topk_apply_bound has no k).
+// Header words: [0] ovf_count, [1] the exact path's slow-list count, [2]
+// band_built: 0 after a screen (the finish compacts the band from the append
+// lists, ucut = (-inf, eps) from the scan), 1 once cand / cand_cnt / ucut /
+// ovf_flag hold a band (ip_select_kernel via nrk_ip_topk_bound) or the
+// screen's no-band marking (no items, k > IP_KFAST).
 struct IpWs {
     int32_t* ovf_count;
     float2* ucut;
@@ -3153,7 +3270,7 @@ static void launch_scan_v(const float* users, int n_users, const uint8_t* cat, i
     const unsigned grid = (unsigned)((n_users + per_wg - 1) / per_wg);
     ip_scan_kernel<DP, NW, NSL, UG, MT><<<grid, NW * 64, 0, s>>>(
         users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, r.t_lo, r.t_hi, r.n_pre, r.pstride,
-        w.bnd, w.bnd_m);
+        w.bnd, w.bnd_m, w.ucut);
 }
 
 // ring slots of the D = 32, k <= 32 scan (config 2): 4 (one more tile in
@@ -3179,7 +3296,7 @@ static void launch_scan(const float* users, int n_users, const uint8_t* cat, int
         const int insp = w.bnd != nullptr ? SCAN_WS_SHARD_INSP : SCAN_WS_INSP;
         ip_scan_ws_kernel<DP, SCAN_NSL4, MT><<<grid, 256 * (1 + SCAN_WS_NB), 0, s>>>(
             users, n_users, cat, n_items, dim, k, w.m2, w.app, w.acnt, w.uinfo, r.t_lo, r.t_hi, r.n_pre, r.pstride,
-            w.bnd, w.bnd_m, insp);
+            w.bnd, w.bnd_m, insp, w.ucut);
     } else {
         constexpr int UG = (DP <= 128 && MT <= 32) ? 2 : 1;
         // 8 waves share a 3-slot ring, 2 workgroups (4 waves / SIMD) per CU; every
@@ -3262,9 +3379,9 @@ static void launch_exact(const float* users, int64_t n_users, const float* items
     lds_limit_once(fallback_set, (const void*)ip_fallback_kernel, lds_max);
     const int grid = (int)std::min<int64_t>(n_users, FB_GRID);
     ip_exact_kernel<<<grid, 256, lds, s>>>(users, items, n_items, dim, k, ns, row_offset, w.ovf_list, w.ovf_count,
-                                           out_s, out_r, out_e, w.fbk, w.slow_list, w.ovf_count + 1);
+                                           out_s, out_r, out_e, w.fbk, w.slow_list, w.ovf_count + 1, (int)n_users);
     ip_fallback_kernel<<<grid, 256, lds, s>>>(users, items, n_items, dim, k, ns, row_offset, w.slow_list,
-                                              w.ovf_count + 1, out_s, out_r, out_e);
+                                              w.ovf_count + 1, out_s, out_r, out_e, (int)n_users);
 }
 
 // The one-wave-per-user sorts (ip_bound, ip_apply_bound, topk_merge) by their
@@ -3305,7 +3422,8 @@ static void launch_refine(const float* users, int64_t n_users, const float* item
     auto go = [&](auto ds4, auto sv, auto fk) {
         ip_refine_kernel<decltype(ds4)::value, decltype(sv)::value, decltype(fk)::value><<<g2, 256, 0, s>>>(
             users, n_users, items, cat, n_items, dim, k, row_offset, b.cand, b.bandcap, b.cnt, b.ucut, w.ovf_flag,
-            w.ovf_list, w.ovf_count, out_s, out_r, out_e, b.n_src, b.src_users, b.x_cap, b.src_cnt);
+            w.ovf_list, w.ovf_count, w.ovf_count + WS_BAND_BUILT, w.app, w.m2, w.acnt, w.uinfo, out_s, out_r, out_e,
+            b.n_src, b.src_users, b.x_cap, b.src_cnt);
     };
     auto by_sv = [&](auto ds4) {
         if (k > 64) go(ds4, std::integral_constant<int, 256>{}, std::false_type{});
@@ -3398,8 +3516,8 @@ static int ip_check(const float* users, int64_t n_users, const float* items, con
     return NRK_OK;
 }
 
-// phases: 1 = the MFMA scan, 2 = the select (or the exact-path / empty
-// marking), 3 = both
+// phases: 1 = the MFMA scan, 2 = the cleared workspace header (plus the
+// exact-path / empty marking where there is no scan), 3 = both
 static int screen_phases(const float* users, int64_t n_users, const void* catalog, int64_t n_items, int dim, int k,
                          int64_t blk_lo, int64_t blk_hi, void* workspace, size_t workspace_bytes,
                          nrk_stream_t stream, int phases) {
@@ -3422,14 +3540,14 @@ static int screen_phases(const float* users, int64_t n_users, const void* catalo
             (void)hipMemsetAsync(w.cnt, 0, (size_t)n_users * sizeof(int32_t), s);
             (void)hipMemsetAsync(w.ovf_flag, 0, (size_t)n_users * sizeof(int32_t), s);
             (void)hipMemsetAsync(w.ucut, 0xFF, (size_t)n_users * sizeof(float2), s);  // NaN cut: no band
+            (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.ovf_count + WS_BAND_BUILT), 1, 1, s);
         } else if (k > IP_KFAST) {
             ip_all_exact_kernel<<<grid_for(n_users, 256, 4096), 256, 0, s>>>(n_users, w.cnt, w.ovf_flag, w.ovf_list,
                                                                              w.ovf_count);
-        } else {
-            ip_select_kernel<<<sh_grid(n_users), 256, 0, s>>>(n_users, k, w.m2, w.bandcap, w.app, w.acnt, w.uinfo,
-                                                              w.cand, w.cnt, w.ucut, w.ovf_flag, w.ovf_list,
-                                                              w.ovf_count);
         }
+        // else: the cleared header (band_built = 0) is all: the finish compacts
+        // the band from the append lists (ip_select_kernel only runs for
+        // nrk_ip_topk_bound, whose callers need theta's band)
     }
     NRK_CHECK_LAUNCH();
     return NRK_OK;
@@ -3504,6 +3622,13 @@ int nrk_ip_topk_bound(const float* users, int64_t n_users, const void* catalog, 
     if (n_items == 0) {
         // empty shard: no bound (the screen wrote no band)
         (void)hipMemsetAsync(w.cnt, 0, (size_t)n_users * sizeof(int32_t), s);
+    } else {
+        // the screen left the append lists: build theta's band from them now
+        // (the select lists its overflowed users afresh and sets band_built,
+        // so the finish reads this band and the cut nrk_ip_topk_apply_bound raises)
+        NRK_FILL(__func__, w.ovf_count, 0, 256, s);
+        ip_select_kernel<<<sh_grid(n_users), 256, 0, s>>>(n_users, k, w.m2, w.bandcap, w.app, w.acnt, w.uinfo, w.cand,
+                                                          w.cnt, w.ucut, w.ovf_flag, w.ovf_list, w.ovf_count);
     }
     const CatalogHdr* hdr = reinterpret_cast<const CatalogHdr*>(
         reinterpret_cast<const uint8_t*>(catalog) + catalog_body_bytes(n_items, pad_dim(dim)));

@@ -425,7 +425,7 @@ def topk_merge(exact_lists, row_lists, k_out):
 
 
 def ip_topk_screen(users, catalog: Catalog, k: int, workspace):
-    """Phase 1 of ip_topk (fp16 MFMA scan -> candidate band in ``workspace``).
+    """Phase 1 of ip_topk (fp16 MFMA scan -> per-user append lists in ``workspace``).
     ``users`` must be finite (not checked here: the hot path)."""
     _dev(users, workspace)
     n = users.shape[0]
@@ -441,7 +441,9 @@ def ip_topk_scan(users, catalog: Catalog, k: int, workspace):
 
 
 def ip_topk_select(users, catalog: Catalog, k: int, workspace):
-    """ip_topk_screen's second launch alone: the per-user select (band)."""
+    """ip_topk_screen's second part alone: the cleared workspace header (the
+    finish then takes its band from the scan's append lists; the per-user
+    select runs in ip_topk_bound)."""
     _dev(users, workspace)
     _lib.call("nrk_ip_topk_select", _ptr(users), users.shape[0], _ptr(catalog.packed), catalog.n, catalog.d, k,
               _ptr(workspace), workspace.numel(), _stream())
