@@ -274,6 +274,28 @@ int nrk_topk_merge(const double* in_exact, const int32_t* in_rows, int n_lists,
                    int64_t list_stride, int64_t n_users, int k_in, int k_out, float* out_scores,
                    int32_t* out_rows, double* out_exact, nrk_stream_t stream);
 
+/* nrk_ip_topk's contract for a SMALL user batch (the serving case: one
+ * faiss_index.search per recall(user_id), youtubednn_recaller.py:520).
+ * nrk_ip_topk gives 1,024 users to a workgroup, so a few users run on one
+ * compute unit; this path splits the catalog across the chip instead: every
+ * workgroup scores its slices of the fp32 rows exactly against a tile of
+ * users and keeps a streaming top-k, one workgroup per user merges the lists.
+ * No packed catalog is read.  Bit-identical outputs to nrk_ip_topk (rows,
+ * fp32 scores, fp64 scores; the -1 / -FLT_MAX / -inf padding past n_items).
+ * 1 <= k <= 128 (larger: NRK_EUNSUPPORTED, use nrk_ip_topk), dim <= 256,
+ * n_users <= NRK_IP_QUERY_MAX_USERS (the workspace holds one k-entry list per
+ * user and catalog workgroup), n_items < 2^30.  users and items must be
+ * finite.  New: no reference counterpart.
+ *   nrk_ip_query_plan: out = {users per workgroup tile, items per round,
+ *   workgroups along the catalog, list capacity} of such a call -- a pure
+ *   function of its arguments, no device work. */
+#define NRK_IP_QUERY_MAX_USERS 4096
+size_t nrk_ip_query_workspace_bytes(int64_t n_users, int64_t n_items, int dim, int k);
+int nrk_ip_query_plan(int64_t n_users, int64_t n_items, int dim, int k, int32_t out[4]);
+int nrk_ip_query(const float* users, int64_t n_users, const float* items, int64_t n_items, int dim, int k,
+                 int64_t row_offset, float* out_scores, int32_t* out_rows, double* out_exact, void* workspace,
+                 size_t workspace_bytes, nrk_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
 /* Embedding similarity (the second Faiss site)                           */
 /* ---------------------------------------------------------------------- */

@@ -31,6 +31,7 @@
 //      IP_KFAST: exact fp64 radix-select over the whole catalog, then a
 //      workgroup bitonic sort of the k winners.
 #include "nrk_common.h"
+#include "exact_dot.h"
 
 #include <float.h>
 #include <math.h>
@@ -1888,45 +1889,6 @@ __global__ void ip_all_exact_kernel(int64_t n_users, int32_t* __restrict__ cand_
 }
 
 // ------------------------------------------------------------ refinement --
-__device__ __forceinline__ double exact_dot(const float* __restrict__ a, const float* __restrict__ b,
-                                            int dim) {
-    double s = 0.0;
-    if ((dim & 31) == 0) {
-        // 8 float4 of both rows in flight per step (a runtime-dim loop
-        // otherwise waits on each row piece in turn); same sequential order
-        const float4* a4 = reinterpret_cast<const float4*>(a);
-        const float4* b4 = reinterpret_cast<const float4*>(b);
-        for (int t0 = 0; t0 < dim / 4; t0 += 8) {
-            float4 x[8], y[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                x[t] = a4[t0 + t];
-                y[t] = b4[t0 + t];
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                s += (double)x[t].x * (double)y[t].x;
-                s += (double)x[t].y * (double)y[t].y;
-                s += (double)x[t].z * (double)y[t].z;
-                s += (double)x[t].w * (double)y[t].w;
-            }
-        }
-    } else if ((dim & 3) == 0) {
-        const float4* a4 = reinterpret_cast<const float4*>(a);
-        const float4* b4 = reinterpret_cast<const float4*>(b);
-        for (int t = 0; t < dim / 4; ++t) {
-            const float4 x = a4[t], y = b4[t];
-            s += (double)x.x * (double)y.x;
-            s += (double)x.y * (double)y.y;
-            s += (double)x.z * (double)y.z;
-            s += (double)x.w * (double)y.w;
-        }
-    } else {
-        for (int t = 0; t < dim; ++t) s += (double)a[t] * (double)b[t];
-    }
-    return s + 0.0;
-}
-
 // One push into a wave's krow ring (the rows, or codes for them, that passed
 // the prefilter and await an exact round): the lanes with keep append v in
 // lane order from fill position kc; returns the new fill position

@@ -60,6 +60,9 @@ SIGNATURES = {
     "nrk_ip_topk_shard_band": (INT, [I64, I64, INT, INT, P, INT, INT, INT, P, SZ, P, P, P]),
     "nrk_ip_topk_refine_x": (INT, [P, I64, P, P, I64, INT, INT, I64, P, INT, I64, INT, P, P, P, P, P, P, P, SZ,
                                    P]),
+    "nrk_ip_query_workspace_bytes": (SZ, [I64, I64, INT, INT]),
+    "nrk_ip_query_plan": (INT, [I64, I64, INT, INT, P]),
+    "nrk_ip_query": (INT, [P, I64, P, I64, INT, INT, I64, P, P, P, P, SZ, P]),
     "nrk_row_normalize": (INT, [P, I64, INT, P, P, P]),
     "nrk_itemcf_pair_offsets": (INT, [P, I64, P, P]),
     "nrk_itemcf_workspace_bytes": (SZ, [I64, I32]),

@@ -407,6 +407,65 @@ def ip_topk_workspace(n_users, catalog: Catalog, k, device):
     return torch.empty(nb, dtype=torch.uint8, device=device)
 
 
+IP_QUERY_KMAX = 128          # nrk_ip_query's k; larger k is ip_topk's exact path
+IP_QUERY_MAX_USERS = 4096    # NRK_IP_QUERY_MAX_USERS (include/nrk.h)
+
+
+def _ip_query_sizes(n_users, n_items, dim, k):
+    if not (1 <= k <= IP_QUERY_KMAX):
+        raise ValueError(f"k must be in [1, {IP_QUERY_KMAX}] (ip_topk takes larger k)")
+    if not (1 <= dim <= 256):
+        raise ValueError("dim must be in [1, 256]")
+    if not (0 <= n_users <= IP_QUERY_MAX_USERS):
+        raise ValueError(f"n_users must be <= {IP_QUERY_MAX_USERS} (ip_topk takes larger batches)")
+    if not (0 <= n_items < 2 ** 30):
+        raise ValueError("n_items must be < 2^30")
+
+
+def ip_query_plan(n_users: int, n_items: int, dim: int, k: int):
+    """(users per workgroup tile, items per round, workgroups along the
+    catalog, list capacity) of an ip_query call of these sizes; no device work."""
+    import ctypes
+
+    _ip_query_sizes(n_users, n_items, dim, k)
+    out = (ctypes.c_int32 * 4)()
+    _lib.call("nrk_ip_query_plan", n_users, n_items, dim, k, ctypes.cast(out, _P))
+    return tuple(out)
+
+
+def ip_query_workspace(n_users, catalog: Catalog, k, device):
+    _ip_query_sizes(n_users, catalog.n, catalog.d, k)
+    nb = _lib.lib().nrk_ip_query_workspace_bytes(n_users, catalog.n, catalog.d, k)
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def ip_query(users, catalog: Catalog, k: int, row_offset: int = 0, exact: bool = False, workspace=None,
+             check_finite: bool = True):
+    """ip_topk's result for a small user batch (at most IP_QUERY_MAX_USERS
+    users, k <= 128): the catalog is split across the chip instead of the
+    users, every score is the exact one (catalog.items; the packed copy is not
+    read).  Same checks, return shapes and dtypes as ip_topk, bit-identical
+    values."""
+    _need(users, torch.float32, name="users")
+    if users.dim() != 2 or users.shape[1] != catalog.d:
+        raise ValueError(f"users must be [n, {catalog.d}]")
+    n = users.shape[0]
+    _ip_query_sizes(n, catalog.n, catalog.d, k)
+    if check_finite:
+        _finite(users, "users")
+    _dev(users, catalog.items)
+    dev = users.device
+    s = torch.empty((n, k), dtype=torch.float32, device=dev)
+    r = torch.empty((n, k), dtype=torch.int32, device=dev)
+    e = torch.empty((n, k), dtype=torch.float64, device=dev) if exact else None
+    ws_bytes = _lib.lib().nrk_ip_query_workspace_bytes(n, catalog.n, catalog.d, k)
+    if workspace is None or workspace.numel() < ws_bytes:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.call("nrk_ip_query", _ptr(users), n, _ptr(catalog.items), catalog.n, catalog.d, k, int(row_offset),
+              _ptr(s), _ptr(r), _ptr(e), _ptr(workspace), workspace.numel(), _stream())
+    return (s, r, e) if exact else (s, r)
+
+
 def topk_merge(exact_lists, row_lists, k_out):
     """Merge [G, n, k_in] per-shard lists (fp64 scores + global rows)."""
     _dev(exact_lists, row_lists)

@@ -10,7 +10,9 @@ ready -> ``ValueError`` (:508-509).
 What changes is underneath: the user/item towers run as HIP kernels
 (nrk_tt_user_fwd / nrk_tt_item_fwd), the Faiss IndexFlatIP becomes a device
 catalog (nrk_ip_catalog_build) and ``batch_recall`` is ONE device top-k call
-for the whole user list (nrk_ip_topk) instead of one Faiss search per user.
+for the whole user list instead of one Faiss search per user: nrk_ip_topk, or,
+up to ``query_max_users`` users (``recall(user_id)`` is one), nrk_ip_query,
+which splits the catalog across the chip instead of the users.
 ``train`` (:211-423) runs on the GPU as well: the samples are generated on the
 device (nrk_tt_make_samples), every step is one fused forward + loss +
 backward (nrk_tt_train_grad) and one dense-semantics Adam sweep
@@ -40,6 +42,13 @@ def _as_mapping_array(m, n=None):
 
 
 class YoutubeDNNRecaller(BaseRecaller):
+    # batch_recall searches with ops.ip_query up to this many known users (and
+    # topk + 1 <= 128), with ops.ip_topk above; 0 = always ip_topk.  An instance
+    # may override it.  From profiles/r10_query.txt (tools/query_bench.py), the
+    # line "config-2 catalog: largest n_users with every ip_query run below
+    # every ip_topk run = 512", halved for catalogs of other sizes and dims.
+    query_max_users = 256
+
     def __init__(self, config: RecallConfig | None = None, device: str | torch.device = "cuda"):
         super().__init__(config or RecallConfig())
         self.seq_max_len = getattr(self.config, "youtubednn_seq_max_len", 30)
@@ -260,7 +269,10 @@ class YoutubeDNNRecaller(BaseRecaller):
             return results
         rows_needed = torch.as_tensor(idx[known], device=self.device)
         q = self.user_embeddings.index_select(0, rows_needed).contiguous()
-        s, r = ops.ip_topk(q, self.catalog, topk + 1)
+        if q.shape[0] <= min(self.query_max_users, ops.IP_QUERY_MAX_USERS) and topk + 1 <= ops.IP_QUERY_KMAX:
+            s, r = ops.ip_query(q, self.catalog, topk + 1)  # few users: the catalog-split search
+        else:
+            s, r = ops.ip_topk(q, self.catalog, topk + 1)
         s = s[:, 1:].cpu().numpy()  # rank 0 dropped (youtubednn_recaller.py:524)
         r = r[:, 1:].cpu().numpy().astype(np.int64)
         n_map = len(self._item_raw)
