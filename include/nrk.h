@@ -643,6 +643,51 @@ int nrk_fuse_wide(const int64_t* offsets, int64_t n_users, const int32_t* item, 
                   double* out_score, int32_t* out_cnt, nrk_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Cold-start recall                                                      */
+/* ---------------------------------------------------------------------- */
+
+/* ColdStartRecaller (src/recall/coldstart_recaller.py) over dense ids.
+ * Lists: list_off [n_lists + 1], item [n_entries] (row of the item tables, or
+ * -1 = missing from one of the three item dicts, :86-91), score [n_entries]
+ * f64, in list order; prof [n_lists] = row of the profile tables or -1 (the
+ * user is not in user_hist_item_types_dict, :74).  Profile tables: cat_off
+ * [n_prof + 1] / cat [n_cat] (every user's distinct category codes,
+ * ascending), mean_words, last_created [n_prof] f64.  Item tables [n_items]:
+ * item_type int32, item_words / item_created f64, item_clicked uint8.  A pair
+ * is kept when (:98-115, in f64 with the reference's operations)
+ *   prof >= 0 && item >= 0 && cat contains item_type[item]
+ *   && !item_clicked[item] && !(fabs(item_words[item] - mean_words[p]) > words_tol)
+ *   && !(fabs(item_created[item] - last_created[p]) > time_tol)
+ * so a NaN mean or time keeps the pair, as the reference's `>` does.
+ *
+ * nrk_coldstart_filter replaces _apply_filtering's loop (:71-120) for every
+ * list in one launch: keep [n_entries] uint8 (1 = kept), kept [n_lists] the
+ * count per list.  Lists and category sets of any length.
+ *
+ * nrk_coldstart_recall replaces recall (:139-147) for n_query users in one
+ * launch: q [n_query] = list index or -1 (unknown user: empty).  Per query:
+ * the filter, then the top-k of the survivors by (score desc, position asc)
+ * -- Python's stable sorted(..., reverse=True)[:topk]; -0.0 == +0.0, NaN
+ * scores are the caller's to refuse.  out_pos [n_query, topk] = position
+ * inside the list (-1 padded), out_score [n_query, topk] (0 padded), out_cnt
+ * [n_query].  cap in [1, 2048] is the survivor capacity per user (LDS slots):
+ * a user with more survivors gets out_cnt = -1 and padded rows.  topk in
+ * [1, 2048].  No workspace, no allocation, no host sync. */
+int nrk_coldstart_filter(const int64_t* list_off, int64_t n_lists, const int32_t* item, int64_t n_entries,
+                         const int32_t* prof, const int64_t* cat_off, const int32_t* cat, int64_t n_cat,
+                         const double* mean_words, const double* last_created, int64_t n_prof,
+                         const int32_t* item_type, const double* item_words, const double* item_created,
+                         const uint8_t* item_clicked, int64_t n_items, double words_tol, double time_tol,
+                         uint8_t* keep, int32_t* kept, nrk_stream_t stream);
+int nrk_coldstart_recall(const int64_t* q, int64_t n_query, const int64_t* list_off, int64_t n_lists,
+                         const int32_t* item, const double* score, int64_t n_entries, const int32_t* prof,
+                         const int64_t* cat_off, const int32_t* cat, int64_t n_cat, const double* mean_words,
+                         const double* last_created, int64_t n_prof, const int32_t* item_type,
+                         const double* item_words, const double* item_created, const uint8_t* item_clicked,
+                         int64_t n_items, double words_tol, double time_tol, int cap, int topk, int32_t* out_pos,
+                         double* out_score, int32_t* out_cnt, nrk_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Ranker context features                                                */
 /* ---------------------------------------------------------------------- */
 

@@ -90,6 +90,9 @@ SIGNATURES = {
     "nrk_fuse_minmax": (INT, [P, I64, P, P]),
     "nrk_fuse": (INT, [P, I64, P, P, P, P, INT, P, INT, INT, F64, F64, P, P, P, P, INT, P, P, P, P]),
     "nrk_fuse_wide": (INT, [P, I64, P, P, P, P, INT, P, INT, INT, F64, F64, P, P, P, P, INT, INT, P, P, P, P]),
+    "nrk_coldstart_filter": (INT, [P, I64, P, I64, P, P, P, I64, P, P, I64, P, P, P, P, I64, F64, F64, P, P, P]),
+    "nrk_coldstart_recall": (INT, [P, I64, P, I64, P, P, I64, P, P, P, I64, P, P, I64, P, P, P, P, I64, F64, F64,
+                                   INT, INT, P, P, P, P]),
     "nrk_ctx_features": (INT, [P, P, P, P, P]),
     "nrk_din_remap_index": (INT, [P, I64, INT, P, INT, P, P]),
     "nrk_din_prep_bytes": (SZ, [INT, I64]),

@@ -10,6 +10,9 @@ user ids, group rows in sorted-frame order).
 ``item_created_time`` == ItemFeatureExtractor.get_item_info_dict's
 created-time dict (extractors.py:136-164): sklearn MinMaxScaler over the
 whole article table.
+
+``user_hist_item_info`` / ``item_info`` == the two extractors behind
+ColdStartRecaller's inputs (extractors.py:65-131, :136-164).
 """
 from __future__ import annotations
 
@@ -76,6 +79,37 @@ def item_created_time(item_info_df):
 
     x = MinMaxScaler().fit_transform(item_info_df[["created_at_ts"]])[:, 0]
     return dict(zip(item_info_df["click_article_id"], x))
+
+
+def item_info(item_info_df):
+    """(item_type_dict, item_words_dict, item_created_time_dict) ==
+    ItemFeatureExtractor.get_item_info_dict (extractors.py:136-164): the
+    article table's category and word count per item and its created time
+    MinMax-scaled over the whole table, with the reference's sklearn call."""
+    ids = item_info_df["click_article_id"]
+    return (dict(zip(ids, item_info_df["category_id"])), dict(zip(ids, item_info_df["words_count"])),
+            item_created_time(item_info_df))
+
+
+def user_hist_item_info(click_df):
+    """(types, ids, mean words, last created time) per user ==
+    UserFeatureExtractor.get_user_hist_item_info_dict (extractors.py:65-131),
+    from the click log merged with the article table.  The same pandas and
+    sklearn operations, so the values are the reference's to the bit: set
+    aggregations per user, pandas' groupby mean of the word counts, and the
+    created time of the last row per user after the (unstable)
+    ``sort_values("click_timestamp")``, MinMax-scaled over the users."""
+    from sklearn.preprocessing import MinMaxScaler
+
+    by_user = click_df.groupby("user_id")
+    types = by_user["category_id"].agg(set)
+    ids = by_user["click_article_id"].agg(set)
+    words = by_user["words_count"].agg("mean")
+    last = click_df.sort_values("click_timestamp").groupby("user_id")["created_at_ts"].apply(
+        lambda x: x.iloc[-1]).reset_index()
+    last["created_at_ts"] = MinMaxScaler().fit_transform(last[["created_at_ts"]])
+    return (dict(zip(types.index, types)), dict(zip(ids.index, ids)), dict(zip(words.index, words)),
+            dict(zip(last["user_id"], last["created_at_ts"])))
 
 
 def item_topk_click(click_df, k=50):

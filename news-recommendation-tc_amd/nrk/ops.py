@@ -1301,6 +1301,110 @@ def usercf_recall(q_slot, offsets, items, nbr_cols, nbr_vals, nbr_cnt, loc_w, cr
     return oi, osc, osrc, ocnt
 
 
+# ------------------------------------------------------------- cold start --
+CS_MAX = 2048          # survivors per user and topk of nrk_coldstart_recall
+CS_WORDS_TOL = 200.0   # coldstart_recaller.py:108
+CS_TIME_TOL = 0.25     # coldstart_recaller.py:114
+
+
+def _coldstart_inputs(list_off, item, prof, cat_off, cat, mean_words, last_created, item_type, item_words,
+                      item_created, item_clicked, validate):
+    """dtype / shape checks of the arguments both cold-start ops share and,
+    with ``validate``, the range checks (device reductions and host reads): a
+    row out of range is an out-of-bounds access on the device.  ``item`` may
+    have any shape ([U, K] rows of ip_topk); it is read flat, in list order.
+    Returns the argument tuple of the C entry points from list_off to n_items
+    (score left out) and the device."""
+    dev = _dev(list_off, item, prof, cat_off, cat, mean_words, last_created, item_type, item_words, item_created,
+               item_clicked)
+    _need(list_off, torch.int64, name="list_off")
+    _need(item, torch.int32, name="item")
+    _need(cat_off, torch.int64, name="cat_off")
+    _need(cat, torch.int32, name="cat")
+    if list_off.dim() != 1 or list_off.numel() < 1 or cat_off.dim() != 1 or cat_off.numel() < 1 or cat.dim() != 1:
+        raise ValueError("list_off / cat_off must be 1-D with rows + 1 entries, cat 1-D")
+    n_lists, n_prof, n_items, n = list_off.numel() - 1, cat_off.numel() - 1, item_type.numel(), item.numel()
+    _need(prof, torch.int32, (n_lists,), "prof")
+    _need(mean_words, torch.float64, (n_prof,), "mean_words")
+    _need(last_created, torch.float64, (n_prof,), "last_created")
+    _need(item_type, torch.int32, (n_items,), "item_type")
+    _need(item_words, torch.float64, (n_items,), "item_words")
+    _need(item_created, torch.float64, (n_items,), "item_created")
+    _need(item_clicked, torch.uint8, (n_items,), "item_clicked")
+    if max(n, n_prof, n_items) >= 2**31:
+        raise ValueError("entries, profile rows and item rows must be < 2^31")
+    if validate:
+        for off, m, what in ((list_off, n, "list"), (cat_off, cat.numel(), "cat")):
+            if int(off[0]) != 0 or int(off[-1]) != m or bool((off[1:] < off[:-1]).any()):
+                raise ValueError(f"{what} offsets must be non-decreasing from 0 to the number of {what} entries")
+        if n and (int(item.min()) < -1 or int(item.max()) >= n_items):
+            raise ValueError(f"item out of [-1, {n_items})")
+        if n_lists and (int(prof.min()) < -1 or int(prof.max()) >= n_prof):
+            raise ValueError(f"prof out of [-1, {n_prof})")
+        if cat.numel() > 1:  # ascending inside every user: the kernel bisects them
+            row = torch.repeat_interleave(torch.arange(n_prof, device=dev), cat_off[1:] - cat_off[:-1])
+            if bool(((row[1:] == row[:-1]) & (cat[1:] <= cat[:-1])).any()):
+                raise ValueError("cat must be strictly ascending inside every user")
+    args = (_ptr(list_off), n_lists, _ptr(item), n, _ptr(prof), _ptr(cat_off), _ptr(cat), cat.numel(),
+            _ptr(mean_words), _ptr(last_created), n_prof, _ptr(item_type), _ptr(item_words), _ptr(item_created),
+            _ptr(item_clicked), n_items)
+    return args, dev
+
+
+def coldstart_filter(list_off, item, prof, cat_off, cat, mean_words, last_created, item_type, item_words,
+                     item_created, item_clicked, words_tol=CS_WORDS_TOL, time_tol=CS_TIME_TOL, validate=True):
+    """ColdStartRecaller._apply_filtering (coldstart_recaller.py:54-126) for
+    every list at once, over dense ids (include/nrk.h: nrk_coldstart_filter).
+    Returns (keep [N] uint8, kept [L] int32)."""
+    args, dev = _coldstart_inputs(list_off, item, prof, cat_off, cat, mean_words, last_created, item_type,
+                                  item_words, item_created, item_clicked, validate)
+    keep = torch.empty(item.numel(), dtype=torch.uint8, device=dev)
+    kept = torch.empty(list_off.numel() - 1, dtype=torch.int32, device=dev)
+    _lib.call("nrk_coldstart_filter", *args, float(words_tol), float(time_tol), _ptr(keep), _ptr(kept), _stream())
+    return keep, kept
+
+
+def coldstart_recall(q, list_off, item, score, prof, cat_off, cat, mean_words, last_created, item_type, item_words,
+                     item_created, item_clicked, topk, words_tol=CS_WORDS_TOL, time_tol=CS_TIME_TOL, validate=True):
+    """ColdStartRecaller.recall (coldstart_recaller.py:128-147) for every query
+    user at once: q [Q] int64 = list index or -1 (unknown user).  score is f64,
+    or fp32 widened here (exact); NaN scores are refused.  Returns (pos
+    [Q, topk] int32 = position inside the list, -1 padded; score [Q, topk] f64;
+    cnt [Q] int32).  More than 2,048 survivors for one user raises
+    NotImplementedError."""
+    if score.dtype == torch.float32:
+        score = score.to(torch.float64)
+    _dev(q, score)
+    _need(q, torch.int64, name="q")
+    _need(score, torch.float64, name="score")
+    if q.dim() != 1 or score.numel() != item.numel():
+        raise ValueError("q must be 1-D and score must have one entry per item")
+    if not (1 <= topk <= CS_MAX):
+        raise NotImplementedError(f"topk must be in [1, {CS_MAX}]")
+    args, dev = _coldstart_inputs(list_off, item, prof, cat_off, cat, mean_words, last_created, item_type,
+                                  item_words, item_created, item_clicked, validate)
+    nq, n_lists = q.numel(), list_off.numel() - 1
+    if nq and (int(q.min()) < -1 or int(q.max()) >= n_lists):
+        raise ValueError(f"q out of [-1, {n_lists})")
+    if score.numel() and bool(torch.isnan(score).any()):
+        raise ValueError("score must not hold NaN")
+    opos = torch.empty((nq, topk), dtype=torch.int32, device=dev)
+    osc = torch.empty((nq, topk), dtype=torch.float64, device=dev)
+    ocnt = torch.empty(nq, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return opos, osc, ocnt
+    # LDS slots per user: the longest queried list bounds its survivors
+    cap = 1
+    if n_lists:
+        lens = (list_off[1:] - list_off[:-1])[q.clamp(min=0)]
+        cap = min(max(int(torch.where(q >= 0, lens, torch.zeros_like(lens)).max()), 1), CS_MAX)
+    _lib.call("nrk_coldstart_recall", _ptr(q), nq, *args[:3], _ptr(score), *args[3:], float(words_tol),
+              float(time_tol), cap, int(topk), _ptr(opos), _ptr(osc), _ptr(ocnt), _stream())
+    if bool((ocnt < 0).any()):
+        raise NotImplementedError(f"more than {CS_MAX} survivors for one user")
+    return opos, osc, ocnt
+
+
 def din_assemble(rec_rows, rec_scores, user_feat, item_feat, user_hist, hist_len, u0, nu, k_use=30, skip=1,
                  n_ctx=16, ctx_bins=10, score_lo=-1.0, score_hi=1.0, seed=23, out=None, validate=True,
                  ctx_width=None):

@@ -15,6 +15,10 @@ lists and tie order).  The z-score normalisation (:155-175) runs on the host
 exactly as the reference does -- numpy mean / std of the method's scores and
 numpy's exp for the sigmoid, so those scores are the reference's to the bit --
 and the device takes them as pre-normalised.
+
+``RecallEnsemble`` (fusion.py:419-556), the online counterpart over recaller
+instances, feeds the same kernel: its merge is the local normalisation with
+the first three strategies.
 """
 from __future__ import annotations
 
@@ -135,20 +139,8 @@ class RecallFusion:
                 seen_off = d(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
                 seen = d(np.where(codes >= 0, codes, -2).astype(np.int32))  # -2 never matches an item code
         strat = STRATEGIES.get(self.fusion_strategy, 1)
-        nu = len(users)
-        o_item = torch.empty((nu, topk), dtype=torch.int32, device=dev)
-        o_score = torch.empty((nu, topk), dtype=torch.float64, device=dev)
-        o_cnt = torch.empty(nu, dtype=torch.int32, device=dev)
-        zm, zs = d(zmean), d(zstd)
-        p = lambda t: P(t.data_ptr()) if t is not None else None  # noqa: E731
-        if max_entries <= FUSE_MAX and topk <= FUSE_MAX:
-            call("nrk_fuse", p(t_off), nu, p(t_item), p(t_score), p(t_m), p(t_rank), len(names), p(t_w), strat,
-                 norm, float(gmin), float(gmax), p(zm), p(zs), p(seen_off), p(seen), int(topk), p(o_item),
-                 p(o_score), p(o_cnt), ops._stream())
-        else:
-            call("nrk_fuse_wide", p(t_off), nu, p(t_item), p(t_score), p(t_m), p(t_rank), len(names), p(t_w),
-                 strat, norm, float(gmin), float(gmax), p(zm), p(zs), p(seen_off), p(seen), max_entries, int(topk),
-                 p(o_item), p(o_score), p(o_cnt), ops._stream())
+        o_item, o_score, o_cnt = _launch_fuse(dev, len(users), t_off, t_item, t_score, t_m, t_rank, t_w, strat, norm,
+                                              gmin, gmax, d(zmean), d(zstd), seen_off, seen, max_entries, topk)
         oi, os_, oc = o_item.cpu().numpy(), o_score.cpu().numpy(), o_cnt.cpu().numpy()
         keys = np.asarray(item_keys, dtype=object)
         raw = keys[np.maximum(oi, 0)] if len(keys) else np.zeros(oi.shape, dtype=object)
@@ -172,6 +164,118 @@ class RecallFusion:
         with open(path, "wb") as fh:
             pickle.dump(self.fused_results, fh)
         return path
+
+
+class RecallEnsemble:
+    """Online counterpart of RecallFusion (fusion.py:419-556): recaller
+    instances, not stored results.  The reference asks every recaller for one
+    user, min-max normalises each list on its own and merges by weighted_avg,
+    weighted_sum or max_score (:488-538) -- RecallFusion's local normalisation
+    with three of its strategies, so the whole batch is one nrk_fuse /
+    nrk_fuse_wide call (norm 0, no seen filter) with bit-identical scores."""
+
+    def __init__(self, config=None, fusion_strategy: str = "weighted_avg", device="cuda"):
+        if fusion_strategy not in ("weighted_avg", "weighted_sum", "max_score"):
+            raise ValueError(f"fusion_strategy must be weighted_avg, weighted_sum or max_score, got {fusion_strategy!r}")
+        self.config = config
+        self.recallers: Dict[str, Dict] = {}
+        self.fusion_strategy = fusion_strategy
+        self.device = torch.device(device)
+
+    def add_recaller(self, name: str, recaller, weight: float = 1.0):
+        """fusion.py:446-456."""
+        self.recallers[name] = {"recaller": recaller, "weight": weight}
+
+    def _collect(self, recaller, users, k):
+        """One recaller's list per user: one batch call when it has one; when
+        that raises (or there is none) user by user, a failure dropping only
+        that user's list from this channel (:476-483)."""
+        if hasattr(recaller, "batch_recall"):
+            try:
+                got = recaller.batch_recall(users, k)
+                return {u: got.get(u, ()) for u in users}
+            except Exception:  # noqa: BLE001 -- the reference swallows any recaller failure
+                pass
+        out = {}
+        for u in users:
+            try:
+                out[u] = recaller.recall(u, topk=k)
+            except Exception:  # noqa: BLE001
+                out[u] = ()
+        return out
+
+    def batch_recall(self, user_ids: List[int], topk: int = 10) -> Dict[int, List[Tuple[int, float]]]:
+        """fusion.py:540-556 with one device merge for the whole batch."""
+        users = list(dict.fromkeys(user_ids))
+        if not users:
+            return {}
+        infos = list(self.recallers.values())
+        per = [self._collect(r["recaller"], users, topk * 2) for r in infos]
+        # every entry, user by user; inside a user in recaller order, then list order
+        it, sc, mt, rk = [], [], [], []
+        counts = np.zeros(len(users), np.int64)
+        for n, u in enumerate(users):
+            for m, res in enumerate(per):
+                lst = res[u]
+                it += [t[0] for t in lst]
+                sc += [t[1] for t in lst]
+                mt += [m] * len(lst)
+                rk += range(len(lst))
+                counts[n] += len(lst)
+        if not it:
+            return {u: [] for u in users}
+        max_entries = int(counts.max())
+        if max_entries > FUSE_WIDE_MAX:
+            raise NotImplementedError(f"more than {FUSE_WIDE_MAX} recalled entries for one user")
+        codes, keys = pd.factorize(_obj(it))
+        weights = np.array([r["weight"] for r in infos], np.float64)
+        mt = np.array(mt, np.int32)
+        if self.fusion_strategy == "weighted_avg" and (weights <= 0).any():
+            # the reference divides by every item's weight sum (:526-529): the sums in its order
+            group = np.repeat(np.arange(len(users)), counts) * len(keys) + codes
+            _, inv = np.unique(group, return_inverse=True)
+            tw = np.zeros(inv.max() + 1)
+            np.add.at(tw, inv, weights[mt])
+            if (tw == 0).any():
+                raise ZeroDivisionError("float division by zero")
+            if (tw < 0).any():
+                raise NotImplementedError("weighted_avg with a negative weight sum")
+        dev = self.device
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        zero = d(np.zeros(len(infos)))
+        o_item, o_score, o_cnt = _launch_fuse(
+            dev, len(users), d(offsets), d(codes.astype(np.int32)), d(np.array(sc, np.float64)), d(mt),
+            d(np.array(rk, np.int32)), d(weights), STRATEGIES[self.fusion_strategy], 0, 0.0, 0.0, zero, zero, None,
+            None, max_entries, topk)
+        oi, os_, oc = o_item.cpu().numpy(), o_score.cpu().numpy(), o_cnt.cpu().numpy()
+        raw = np.asarray(keys, dtype=object)[np.maximum(oi, 0)].tolist()
+        sc_l = os_.tolist()
+        return {u: list(zip(raw[n][:int(oc[n])], sc_l[n][:int(oc[n])])) for n, u in enumerate(users)}
+
+    def recall(self, user_id: int, topk: int = 10) -> List[Tuple[int, float]]:
+        """fusion.py:458-538 (a batch of one)."""
+        return self.batch_recall([user_id], topk)[user_id]
+
+
+def _launch_fuse(dev, n_users, t_off, t_item, t_score, t_m, t_rank, t_w, strat, norm, gmin, gmax, zm, zs, seen_off,
+                 seen, max_entries, topk):
+    """nrk_fuse when every user has at most FUSE_MAX entries and topk fits,
+    else nrk_fuse_wide -> (items [U, topk] int32, scores f64, cnt [U]) on the device."""
+    o_item = torch.empty((n_users, topk), dtype=torch.int32, device=dev)
+    o_score = torch.empty((n_users, topk), dtype=torch.float64, device=dev)
+    o_cnt = torch.empty(n_users, dtype=torch.int32, device=dev)
+    p = lambda t: P(t.data_ptr()) if t is not None else None  # noqa: E731
+    n_methods = t_w.numel()
+    if max_entries <= FUSE_MAX and topk <= FUSE_MAX:
+        call("nrk_fuse", p(t_off), n_users, p(t_item), p(t_score), p(t_m), p(t_rank), n_methods, p(t_w), strat,
+             norm, float(gmin), float(gmax), p(zm), p(zs), p(seen_off), p(seen), int(topk), p(o_item),
+             p(o_score), p(o_cnt), ops._stream())
+    else:
+        call("nrk_fuse_wide", p(t_off), n_users, p(t_item), p(t_score), p(t_m), p(t_rank), n_methods, p(t_w),
+             strat, norm, float(gmin), float(gmax), p(zm), p(zs), p(seen_off), p(seen), max_entries, int(topk),
+             p(o_item), p(o_score), p(o_cnt), ops._stream())
+    return o_item, o_score, o_cnt
 
 
 def _obj(seq):
