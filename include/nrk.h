@@ -688,6 +688,57 @@ int nrk_coldstart_recall(const int64_t* q, int64_t n_query, const int64_t* list_
                          double* out_score, int32_t* out_cnt, nrk_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* User profiles, item popularity, labels                                 */
+/* ---------------------------------------------------------------------- */
+
+/* FeatureExtractor._extract_user_profile_features / _extract_item_features /
+ * _add_labels (src/features/feature_extractor.py:296-438, :752-836) over
+ * dense ids.  The click log is a CSR by user row: u_off [n_users + 1]; inside
+ * a user the clicks in frame order: item (row of the item tables; a row
+ * outside [0, n_items) is an article without a words entry), ts
+ * (click_timestamp), dev_code (dense device-group code in [0, n_codes),
+ * ascending in the raw value).  sorted_item [n_clicks] is the same CSR with
+ * every user's item rows ascending (the caller's key sort); words [n_items]
+ * the word count per item row.
+ *
+ * nrk_profile_user, per user (a user without clicks: zeros, mode and last
+ * item -1):
+ *   out_count    clicks
+ *   out_gap      (double)(max ts - min ts) / (double)(n - 1), 0.0 at n = 1
+ *   out_mean_ts  pandas' groupby mean: the Kahan sum of the float64-cast
+ *                timestamps in frame order / n; (double)sum / n when no
+ *                timestamp is negative and the exact sum is below 2^53, where
+ *                the two agree
+ *   out_mode     x.mode()[0]: the smallest of the most frequent codes
+ *   out_words    (double)(sum of words over the distinct items) / n_distinct
+ *   out_last     item of the maximal timestamp, ties to the later position
+ * n_codes > 64 is NRK_EUNSUPPORTED.
+ *
+ * nrk_profile_item_count: clicks per item row (integer atomics), rows outside
+ * [0, n_items) ignored.
+ *
+ * nrk_profile_scale: sklearn's MinMaxScaler of one column with minmax [2] =
+ * {min, max} on the device (nrk_fuse_minmax): scale = 1 / range (a range
+ * below 10 eps counts as 1), min_ = 0 - min * scale, out = x * scale + min_
+ * as two rounded operations.  skip_zero = 1 leaves entries equal to 0 at 0.0
+ * (the popularity of an unclicked item).
+ *
+ * nrk_profile_labels: out[i] = 1 when last_item[user[i]] == item[i], else 0
+ * (a user or item row of -1: 0); offline = 0 writes -1 everywhere and reads
+ * no input.  No workspace, no allocation, no host sync in any of the four. */
+int nrk_profile_user(const int64_t* u_off, int64_t n_users, const int32_t* item, const int64_t* ts,
+                     const int32_t* dev_code, int64_t n_clicks, int n_codes, const int32_t* sorted_item,
+                     const int64_t* words, int64_t n_items, int64_t* out_count, double* out_gap,
+                     double* out_mean_ts, int32_t* out_mode, double* out_words, int32_t* out_last,
+                     nrk_stream_t stream);
+int nrk_profile_item_count(const int32_t* item, int64_t n_clicks, int64_t n_items, int64_t* out_count,
+                           nrk_stream_t stream);
+int nrk_profile_scale(const double* x, int64_t n, const double* minmax, int skip_zero, double* out,
+                      nrk_stream_t stream);
+int nrk_profile_labels(const int32_t* user, const int32_t* item, int64_t n_pairs, const int32_t* last_item,
+                       int64_t n_users, int offline, int32_t* out, nrk_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Ranker context features                                                */
 /* ---------------------------------------------------------------------- */
 

@@ -93,6 +93,10 @@ SIGNATURES = {
     "nrk_coldstart_filter": (INT, [P, I64, P, I64, P, P, P, I64, P, P, I64, P, P, P, P, I64, F64, F64, P, P, P]),
     "nrk_coldstart_recall": (INT, [P, I64, P, I64, P, P, I64, P, P, P, I64, P, P, I64, P, P, P, P, I64, F64, F64,
                                    INT, INT, P, P, P, P]),
+    "nrk_profile_user": (INT, [P, I64, P, P, P, I64, INT, P, P, I64, P, P, P, P, P, P, P]),
+    "nrk_profile_item_count": (INT, [P, I64, I64, P, P]),
+    "nrk_profile_scale": (INT, [P, I64, P, INT, P, P]),
+    "nrk_profile_labels": (INT, [P, P, I64, P, I64, INT, P, P]),
     "nrk_ctx_features": (INT, [P, P, P, P, P]),
     "nrk_din_remap_index": (INT, [P, I64, INT, P, INT, P, P]),
     "nrk_din_prep_bytes": (SZ, [INT, I64]),

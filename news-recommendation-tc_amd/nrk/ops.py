@@ -1405,6 +1405,90 @@ def coldstart_recall(q, list_off, item, score, prof, cat_off, cat, mean_words, l
     return opos, osc, ocnt
 
 
+# ------------------------------------------------- profiles, popularity, labels --
+def profile_user(u_off, item, ts, dev_code, n_codes, words, n_rows, validate=True):
+    """FeatureExtractor._extract_user_profile_features (feature_extractor.py:
+    296-389) before scaling, for every user at once (include/nrk.h:
+    nrk_profile_user).  u_off [U + 1] int64, item / dev_code [N] int32, ts [N]
+    int64; ``words`` [n_items] int64 with n_items <= n_rows, item rows in
+    [0, n_rows) (a row past the words table is an article without a words
+    entry: distinct, 0 words).  The per-user ascending item rows the kernel
+    dedups over come from one torch sort of (user, item) keys here.  Returns
+    (count int64, gap f64, mean_ts f64, mode int32, mean_words f64, last_item
+    int32), each [U].  More than 64 codes raise NotImplementedError."""
+    dev = _dev(u_off, item, ts, dev_code, words)
+    _need(u_off, torch.int64, name="u_off")
+    if u_off.dim() != 1 or u_off.numel() < 1:
+        raise ValueError("u_off must be 1-D with users + 1 entries")
+    U, N, n_items = u_off.numel() - 1, item.numel(), words.numel()
+    _need(item, torch.int32, (N,), "item")
+    _need(ts, torch.int64, (N,), "ts")
+    _need(dev_code, torch.int32, (N,), "dev_code")
+    _need(words, torch.int64, (n_items,), "words")
+    if not (0 <= n_items <= n_rows < 2**31) or N >= 2**31:
+        raise ValueError("need n_items <= n_rows < 2^31 and fewer than 2^31 clicks")
+    lens = u_off[1:] - u_off[:-1]
+    if validate:
+        if int(u_off[0]) != 0 or int(u_off[-1]) != N or bool((lens < 0).any()):
+            raise ValueError("u_off must be non-decreasing from 0 to the number of clicks")
+        if N and (int(item.min()) < 0 or int(item.max()) >= n_rows):
+            raise ValueError(f"item out of [0, {n_rows})")
+        if N and (int(dev_code.min()) < 0 or int(dev_code.max()) >= n_codes):
+            raise ValueError(f"dev_code out of [0, {n_codes})")
+        # the mean word count is exact in any order while every partial sum is below 2^53
+        if n_items and U and int(words.abs().max()) * max(int(lens.max()), 1) >= 2**53:
+            raise ValueError("word counts too large for an exact sum")
+    row = torch.repeat_interleave(torch.arange(U, dtype=torch.int64, device=dev), lens)
+    key, _ = torch.sort(row * max(n_rows, 1) + item)
+    sorted_item = (key - row * max(n_rows, 1)).to(torch.int32)
+    out = [torch.empty(U, dtype=dt, device=dev) for dt in (torch.int64, torch.float64, torch.float64, torch.int32,
+                                                           torch.float64, torch.int32)]
+    _lib.call("nrk_profile_user", _ptr(u_off), U, _ptr(item), _ptr(ts), _ptr(dev_code), N, int(n_codes),
+              _ptr(sorted_item), _ptr(words), n_items, *(_ptr(o) for o in out), _stream())
+    return tuple(out)
+
+
+def profile_item_count(item, n_items):
+    """Clicks per item row, int64 [n_items] (value_counts of feature_extractor.py:396-398); rows outside
+    [0, n_items) are ignored."""
+    dev = _dev(item)
+    _need(item, torch.int32, name="item")
+    cnt = torch.empty(n_items, dtype=torch.int64, device=dev)
+    _lib.call("nrk_profile_item_count", _ptr(item), item.numel(), n_items, _ptr(cnt), _stream())
+    return cnt
+
+
+def profile_minmax_scale(x, fit=None, skip_zero=False):
+    """sklearn's MinMaxScaler.fit_transform of one f64 column, bit for bit
+    (nrk_fuse_minmax + nrk_profile_scale).  ``fit``: the entries the scaler is
+    fitted on (default: x itself).  ``skip_zero`` leaves zeros at 0.0."""
+    dev = _dev(x, fit)
+    _need(x, torch.float64, name="x")
+    fit = x if fit is None else fit
+    _need(fit, torch.float64, name="fit")
+    mm = torch.zeros(2, dtype=torch.float64, device=dev)
+    if fit.numel():
+        _lib.call("nrk_fuse_minmax", _ptr(fit), fit.numel(), _ptr(mm), _stream())
+    out = torch.empty_like(x)
+    _lib.call("nrk_profile_scale", _ptr(x), x.numel(), _ptr(mm), 1 if skip_zero else 0, _ptr(out), _stream())
+    return out
+
+
+def profile_labels(user_rows, item_rows, last_item, offline=True):
+    """FeatureExtractor._add_labels (feature_extractor.py:752-836) for (user
+    row, item row) pairs, -1 = unknown: int32 [n], 1 where the item is the
+    user's last click, else 0; -1 everywhere in online mode."""
+    dev = _dev(user_rows, item_rows, last_item)
+    n = user_rows.numel()
+    _need(user_rows, torch.int32, (n,), "user_rows")
+    _need(item_rows, torch.int32, (n,), "item_rows")
+    _need(last_item, torch.int32, name="last_item")
+    out = torch.empty(n, dtype=torch.int32, device=dev)  # the kernel bounds-checks the rows: no sync here
+    _lib.call("nrk_profile_labels", _ptr(user_rows), _ptr(item_rows), n, _ptr(last_item), last_item.numel(),
+              1 if offline else 0, _ptr(out), _stream())
+    return out
+
+
 def din_assemble(rec_rows, rec_scores, user_feat, item_feat, user_hist, hist_len, u0, nu, k_use=30, skip=1,
                  n_ctx=16, ctx_bins=10, score_lo=-1.0, score_hi=1.0, seed=23, out=None, validate=True,
                  ctx_width=None):
