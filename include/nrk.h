@@ -798,6 +798,52 @@ typedef struct {
 int nrk_ctx_features(const nrk_ctx_tables* tables, const nrk_ctx_spec* spec, double* out_raw, int32_t* out_codes,
                      nrk_stream_t stream);
 
+/* The order statistics a context spec is fitted from (_apply_binning's
+ * nunique / median / fillna and the ranks np.percentile interpolates between),
+ * of n_cols columns of the raw feature matrix nrk_ctx_features writes.  Every
+ * requested column is turned into order-preserving u64 keys (-0.0 = +0.0, NaN
+ * last), sorted (keys-only LSD radix sort, one segment per column) and
+ * summarised; the interpolation of the edges is the caller's (nrk/features.py
+ * _finish_edges).  No host sync, no allocation; the result depends only on the
+ * multiset of each column's values.
+ *   raw        device, row-major [n_rows, ld] f64
+ *   cols       HOST [n_cols] column indices (any order, < ld)
+ *   col_kind   HOST [n_cols] 0 = f64, 1 = f32, 2 = integer-valued: the dtype the
+ *              even-count median is formed in ((a + b) / 2 in f32 for kind 1);
+ *              a valid value that kind 1 / 2 cannot hold sets `inexact`
+ *   ranks      HOST [n_ranks] ascending ranks in [0, n_rows) into the FILLED
+ *              sorted column: the sorted valid values with the n_rows - n_valid
+ *              NaN rows replaced by `fill` at its place; n_ranks <= 64
+ *   out_stats  device [n_cols]
+ *   out_picks  device [n_cols, n_ranks] the filled column's value at each rank
+ * n_rows == 0 is NRK_OK with nothing launched; n_rows >= 2^31 is
+ * NRK_EUNSUPPORTED; n_cols is in [1, 64]. */
+typedef struct {
+    int64_t n_valid;      /* rows that are not NaN                                   */
+    int64_t n_distinct;   /* distinct valid values                                   */
+    double vmin, vmax;    /* of the valid values (0 when there is none)              */
+    double mid_lo, mid_hi; /* the two middle valid values (equal when n_valid is odd) */
+    double fill;          /* the median in the column's kind; 0 when n_valid == 0    */
+    int64_t n_lt_fill;    /* valid values below fill                                 */
+    int64_t n_eq_fill;    /* valid values equal to fill                              */
+    double small[21];     /* the min(n_distinct, 21) smallest distinct values, ascending; then 0 */
+    int64_t inexact;      /* 1: some valid value is not representable in the kind    */
+} nrk_ctx_fit_col;
+
+size_t nrk_ctx_fit_workspace_bytes(int64_t n_rows, int32_t n_cols); /* 0: arguments out of range */
+int32_t nrk_ctx_fit_tile(void);                                     /* keys per sort tile */
+int nrk_ctx_fit_stats(const double* raw, int64_t n_rows, int32_t ld, const int32_t* cols, const int32_t* col_kind,
+                      int32_t n_cols, const int64_t* ranks, int32_t n_ranks, nrk_ctx_fit_col* out_stats,
+                      double* out_picks, void* workspace, size_t workspace_bytes, nrk_stream_t stream);
+/* After nrk_ctx_fit_stats, on the workspace it left (same n_rows, n_cols, not
+ * written since): out_counts[c, p] = valid values of column c below
+ * probes[c, p] (device [n_cols, n_probes] each, n_probes <= 64; a NaN probe
+ * counts 0).  With the candidate bin edges as probes the differences say which
+ * bins hold a row, i.e. the classes the reference's LabelEncoder sees. */
+int nrk_ctx_fit_count_below(int64_t n_rows, int32_t n_cols, const double* probes, int32_t n_probes,
+                            int64_t* out_counts, const void* workspace, size_t workspace_bytes,
+                            nrk_stream_t stream);
+
 /* ---- multi-GPU exchanges over RCCL --------
  * For a caller binding the C ABI without torch.distributed: one process per
  * GPU; rank 0 makes a unique id (nrk_rccl_unique_id_bytes() bytes), the

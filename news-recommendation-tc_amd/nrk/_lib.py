@@ -98,6 +98,10 @@ SIGNATURES = {
     "nrk_profile_scale": (INT, [P, I64, P, INT, P, P]),
     "nrk_profile_labels": (INT, [P, P, I64, P, I64, INT, P, P]),
     "nrk_ctx_features": (INT, [P, P, P, P, P]),
+    "nrk_ctx_fit_workspace_bytes": (SZ, [I64, I32]),
+    "nrk_ctx_fit_tile": (I32, []),
+    "nrk_ctx_fit_stats": (INT, [P, I64, I32, P, P, I32, P, I32, P, P, P, SZ, P]),
+    "nrk_ctx_fit_count_below": (INT, [I64, I32, P, I32, P, P, SZ, P]),
     "nrk_din_remap_index": (INT, [P, I64, INT, P, INT, P, P]),
     "nrk_din_prep_bytes": (SZ, [INT, I64]),
     "nrk_din_prepare": (INT, [P, INT, P, INT, I64, P, P]),

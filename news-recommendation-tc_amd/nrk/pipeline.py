@@ -123,15 +123,39 @@ class FusedRecallRank:
         from .features import ctx_features
 
         tables, spec = self.ctx
+        groups, score = self._chunk_groups(rec_scores, u0, nu)
+        P = nu * self.k
+        _, codes = ctx_features(tables, None, a["cand"][:P], score, spec, raw=False, groups=groups,
+                                out_codes=a["ctx"][:P])
+        return codes
+
+    def _chunk_groups(self, rec_scores, u0, nu):
+        """One group of k pairs per user of the chunk, and the pairs' scores."""
         dev = rec_scores.device
         k = self.k
         goff = torch.arange(0, (nu + 1) * k, k, dtype=torch.int64, device=dev)
         guser = torch.arange(u0, u0 + nu, dtype=torch.int32, device=dev)
         score = rec_scores[u0:u0 + nu, 1:k + 1].to(torch.float64).reshape(-1).contiguous()
-        P = nu * k
-        _, codes = ctx_features(tables, None, a["cand"][:P], score, spec, raw=False, groups=(goff, guser, None),
-                                out_codes=a["ctx"][:P])
-        return codes
+        return (goff, guser, None), score
+
+    def fit_ctx(self, tables, rec_scores, rec_rows, n_bins=10, strategy="quantile", max_users=None):
+        """The context spec fitted over the recalled pairs themselves: the raw
+        features of every pair (rank 0 dropped, as in ``rank``) are written
+        chunk by chunk into one device buffer and ``CtxSpec.fit_device`` fits
+        on it, so no raw column leaves the device.  ``max_users``: fit on the
+        first users only."""
+        from .features import CtxSpec, ctx_feature_names, ctx_features
+
+        n = rec_rows.shape[0] if max_users is None else min(int(max_users), rec_rows.shape[0])
+        k = self.k
+        F = 1 + 3 * tables.last_n + 6
+        raw = torch.empty((n * k, F), dtype=torch.float64, device=rec_rows.device)
+        for u0 in range(0, n, self.chunk):
+            nu = min(self.chunk, n - u0)
+            groups, score = self._chunk_groups(rec_scores, u0, nu)
+            cand = rec_rows[u0:u0 + nu, 1:k + 1].to(torch.int32).reshape(-1).contiguous()
+            ctx_features(tables, None, cand, score, None, groups=groups, out_raw=raw[u0 * k:(u0 + nu) * k])
+        return CtxSpec.fit_device(raw, ctx_feature_names(tables.last_n), n_bins=n_bins, strategy=strategy)
 
     def __call__(self, users):
         s, r = self.recall(users)
