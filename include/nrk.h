@@ -63,6 +63,12 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
                     const float* b0, int h0, const float* w1, const float* b1, int h1,
                     float* out, nrk_stream_t stream);
 
+/* Users that one wave pass of nrk_tt_user_fwd's kernel handles together at
+ * (dim, h0): 4 with h0 <= 64, and 0 where the one-user-per-wave kernel runs
+ * (h0 > 64).  No device work.  0 with the error set for a dim or an h0 that
+ * nrk_tt_user_fwd rejects. */
+int nrk_tt_user_pass_users(int dim, int h0);
+
 /* Item tower.  Replaces get_item_embedding (:184-188) + numpy re-norm
  * (:485-489): out[r] = renorm(normalize(E_i[ids[r]])). */
 /* The user tower at any depth (youtubednn_hidden_units of any length,

@@ -4,7 +4,8 @@
 // as _extract_embeddings drives it (:425-470), fused with the numpy
 // re-normalisation of :467-470.  Item tower: get_item_embedding (:184-188)
 // fused with :485-489.  Memory-bound gathers (1 + T rows of D fp32 per user)
-// feeding a 2-layer MLP that fits in LDS; one wave per user.
+// feeding a 2-layer MLP that fits in LDS; four users per wave pass at
+// h0 <= 64 (tt_user_kernel_pass), one wave per user otherwise.
 #include "tower_common.h"
 
 namespace nrk {
@@ -184,6 +185,236 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void t
     if (pu >= 0 && lane < h1) out[pu * h1 + lane] = pout;
 }
 
+// tt_user_kernel at h0 <= 64 with TT_PASS_G users per wave pass: the
+// one-user form re-reads both layers' weights from LDS for every user, adds
+// one scalar term per instruction and runs layer 1 on D of the 64 lanes.  Here
+// a weight read is shared by the pass's four users, the chains advance two
+// users per packed instruction and layer 1 fills the wave (lane l: output
+// l % D of the 4 D / 64 users of group l / D).  Every user's arithmetic is
+// tt_user_kernel's, operation for operation: the per-phase t-ascending history
+// sums, the xor fold of the phases, / (len + 1e-8f), the q-ascending chains
+// z = z + RN(w[q] * x[q]) from the bias, and the two norms as that kernel is
+// compiled: wave_sum_f32's first level is fma(v, v, the other half's square)
+// there, which at D < 64 adds the idle half's +0.0f to the square and changes
+// no bit, as do the levels down to D; the levels below D are plain adds.
+// (The name starts with tt_user_kernel so that the bench's busy report, which
+// looks the tower up by that prefix, finds whichever of the two ran.)
+constexpr int TT_PASS_G = 4;
+constexpr int tt_pass_tile(int dim) { return 2 * dim * TT_PASS_G + 64 * TT_PASS_G; }  // floats per wave: xs | ys
+template <int N>
+using fvec = float __attribute__((ext_vector_type(N)));
+typedef fvec<2> f32x2;
+typedef fvec<4> f32x4;
+
+template <int D>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void tt_user_kernel_pass(
+    const float* __restrict__ user_table, const float* __restrict__ item_table,
+    const int32_t* __restrict__ uid, const int32_t* __restrict__ hist,
+    const int32_t* __restrict__ hist_len, int64_t n, int T, const float* __restrict__ w0,
+    const float* __restrict__ b0, int h0, const float* __restrict__ w1,
+    const float* __restrict__ b1, float* __restrict__ out) {
+    static_assert(D == 16 || D == 32 || D == 64, "tt_user_kernel_pass: D in {16, 32, 64}");
+    constexpr int G = TT_PASS_G, h1 = D;
+    constexpr int P = WAVE / D;       // history phases, and lane groups of layer 1
+    constexpr int UL = G * D / WAVE;  // users a lane carries in layer 1 and the norms
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    // weights and biases laid out as in tt_user_kernel (padded rows)
+    const int S0 = 2 * D + 4, h0p = (h0 + 3) & ~3, S1 = h0p + 4;
+    float* sw0 = lds;            // [h0][S0]
+    float* sb0 = sw0 + h0 * S0;  // [h0] (h0p)
+    float* sw1 = sb0 + h0p;      // [h1][S1]
+    float* sb1 = sw1 + h1 * S1;  // [h1]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // per-wave tile.  xs[q][g]: input q of the pass's user g, so one broadcast
+    // 16-B read returns term q for all four.  ys[group][q][UL]: y0[q] of the
+    // group's users, 4 / UL q per 16-B read; before layer 0 the same words
+    // hold the pass's history indices (as bits), [g][phase][t / P]
+    float* xs = sb1 + h1 + wave * tt_pass_tile(D);
+    float* ys = xs + 2 * D * G;
+    for (int i = threadIdx.x; i < h0 * 2 * D; i += blockDim.x) sw0[(i / (2 * D)) * S0 + i % (2 * D)] = w0[i];
+    for (int i = threadIdx.x; i < h0; i += blockDim.x) sb0[i] = b0[i];
+    for (int i = threadIdx.x; i < h1 * h0; i += blockDim.x) sw1[(i / h0) * S1 + i % h0] = w1[i];
+    for (int i = threadIdx.x; i < h1; i += blockDim.x) sb1[i] = b1[i];
+    __syncthreads();  // the only block barrier: the pass loop below is per wave
+
+    constexpr int CH = 4;  // history rows in flight per lane and user (8 slots a round)
+    const int d = lane % D, ph = lane / D;
+    const int64_t npass = (n + G - 1) / G, pstride = (int64_t)__builtin_amdgcn_readfirstlane(gridDim.x) * 4;
+    // the next pass's lengths, ids (wave-uniform) and history indices (lane t
+    // holds slot t) are loaded while this pass runs; users past n: len 0, row 0
+    auto meta = [&](int64_t pp, int (&len)[G], int32_t (&uidv)[G], int32_t (&hv)[G]) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int64_t uu = pp * G + g;
+            const bool ok = uu < n;
+            len[g] = ok ? hist_len[uu] : 0;
+            uidv[g] = ok ? uid[uu] : 0;
+            hv[g] = ok && lane < T ? hist[uu * T + lane] : 0;
+        }
+    };
+    int64_t p = (int64_t)blockIdx.x * 4 + wave;
+    int len[G];
+    int32_t uidv[G], hv[G];
+    meta(p, len, uidv, hv);
+    // a pass's rows are stored during the next pass, behind its first gathers
+    // (see tt_user_kernel); lane l keeps column l % D of its group's UL rows
+    float pout[UL] = {};
+    int64_t prev = -1;  // the pass whose rows are pending
+    auto store_rows = [&]() {
+        const int64_t r0 = prev * G + UL * ph;
+#pragma unroll
+        for (int j = 0; j < UL; ++j)
+            if (r0 + j < n) out[(r0 + j) * h1 + d] = pout[j];
+        prev = -1;
+    };
+    for (; p < npass; p += pstride) {
+        int nlen[G];
+        int32_t nuid[G], nhv[G];
+        meta(p + pstride, nlen, nuid, nhv);
+        float xu[G], sum[G];
+        int nit[G], nl[G], nitmax = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            xu[g] = user_table[(int64_t)uidv[g] * D + d];
+            ys[g * 64 + (lane % P) * D + lane / P] = __int_as_float(hv[g]);
+            sum[g] = 0.0f;
+            // a length past T (outside the contract) gathers T slots: the
+            // index tile holds no more
+            const int ln = len[g] < T ? len[g] : T;
+            nit[g] = (ln + P - 1) / P;      // slots of phase 0, wave-uniform
+            nl[g] = (ln + P - 1 - ph) / P;  // live slots of this lane's phase
+            nitmax = nit[g] > nitmax ? nit[g] : nitmax;
+        }
+        wave_sync_lds();
+        // slot t = ph + P i of user g; a user's rounds stop at its own nit, a
+        // slot past the length reads row 0 and is not added
+        for (int i0 = 0; i0 < nitmax; i0 += CH) {
+            float v[G][CH];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (i0 < nit[g]) {
+                    const f32x4 r4 = *reinterpret_cast<const f32x4*>(ys + g * 64 + ph * D + i0);
+#pragma unroll
+                    for (int e = 0; e < CH; ++e) {
+                        const uint32_t r = i0 + e < nl[g] ? (uint32_t)__float_as_int(r4[e]) : 0u;
+                        v[g][e] = item_table[(int64_t)r * D + d];
+                    }
+                }
+            }
+            if (i0 == 0 && prev >= 0) store_rows();
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (i0 < nit[g]) {
+#pragma unroll
+                    for (int e = 0; e < CH; ++e)
+                        if (i0 + e < nl[g]) sum[g] += v[g][e];  // t ascending
+                }
+            }
+        }
+        f32x4 xu4, xm4;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#pragma unroll
+            for (int off = D; off < WAVE; off <<= 1) sum[g] += __shfl_xor(sum[g], off, WAVE);
+            xu4[g] = xu[g];
+            xm4[g] = sum[g] / ((float)len[g] + 1e-8f);
+        }
+        wave_sync_lds();  // the indices in ys are read
+        if (lane < D) {  // x[q] = E_u[uid][q], x[D + q] = mean[q]
+            *reinterpret_cast<f32x4*>(xs + lane * G) = xu4;
+            *reinterpret_cast<f32x4*>(xs + (D + lane) * G) = xm4;
+        }
+        wave_sync_lds();
+        {
+            // product and sum rounded separately in every chain of both
+            // layers, and in the norms below (left to the compiler, their
+            // first add would fuse with the square at every D)
+#pragma clang fp contract(off)
+            // layer 0: lane o owns output o for the four users
+            const int o = lane < h0 ? lane : 0;
+            const float* wr0 = sw0 + o * S0;
+            const float bz = lane < h0 ? sb0[lane] : 0.0f;
+            f32x2 z01 = {bz, bz}, z23 = {bz, bz};
+#pragma unroll 2
+            for (int q = 0; q < 2 * D; q += 4) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(wr0 + q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 x = *reinterpret_cast<const f32x4*>(xs + (q + j) * G);
+                    const f32x2 w = {a[j], a[j]};
+                    z01 = z01 + w * x.xy;
+                    z23 = z23 + w * x.zw;
+                }
+            }
+            if (lane < h0) {  // user g: group g / UL, slot g % UL
+                const f32x4 y = {fmaxf(z01.x, 0.0f), fmaxf(z01.y, 0.0f), fmaxf(z23.x, 0.0f), fmaxf(z23.y, 0.0f)};
+                if constexpr (UL == 4) {
+                    *reinterpret_cast<f32x4*>(ys + lane * 4) = y;
+                } else if constexpr (UL == 2) {
+                    *reinterpret_cast<f32x2*>(ys + lane * 2) = y.xy;
+                    *reinterpret_cast<f32x2*>(ys + 128 + lane * 2) = y.zw;
+                } else {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) ys[g * 64 + lane] = y[g];
+                }
+            }
+            wave_sync_lds();
+            // layer 1: lane l owns output l % D for the UL users of group l / D
+            const float* wr = sw1 + d * S1;
+            const float* yp = ys + ph * (64 * UL);
+            fvec<UL> z = (fvec<UL>)(sb1[d]);
+            int q = 0;
+            for (; q + 4 <= h0; q += 4) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(wr + q);
+                float yb[4 * UL];
+#pragma unroll
+                for (int k = 0; k < UL; ++k) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(yp + q * UL + 4 * k);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) yb[4 * k + j] = t[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    fvec<UL> y;
+#pragma unroll
+                    for (int k = 0; k < UL; ++k) y[k] = yb[j * UL + k];
+                    z = z + (fvec<UL>)(a[j]) * y;
+                }
+            }
+            for (; q < h0; ++q) z = z + (fvec<UL>)(wr[q]) * *reinterpret_cast<const fvec<UL>*>(yp + q * UL);
+            float v[UL], nrm[UL];
+#pragma unroll
+            for (int j = 0; j < UL; ++j) v[j] = fmaxf(z[j], 0.0f);
+            wave_sync_lds();  // xs / ys are rewritten by the next pass
+            auto norms = [&]() {
+#pragma unroll
+                for (int j = 0; j < UL; ++j) {
+                    float s = v[j] * v[j];
+                    if constexpr (D == WAVE) s = __builtin_fmaf(v[j], v[j], __shfl_xor(s, 32, WAVE));
+#pragma unroll
+                    for (int m = (D == WAVE ? 16 : D / 2); m > 0; m >>= 1) s = s + __shfl_xor(s, m, WAVE);
+                    nrm[j] = sqrtf(s);
+                }
+            };
+            norms();
+#pragma unroll
+            for (int j = 0; j < UL; ++j) v[j] = v[j] / fmaxf(nrm[j], 1e-12f);
+            norms();
+            if (prev >= 0) store_rows();  // no gathers this pass (every len == 0)
+#pragma unroll
+            for (int j = 0; j < UL; ++j) pout[j] = v[j] / (nrm[j] == 0.0f ? 1.0f : nrm[j]);
+        }
+        prev = p;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            len[g] = nlen[g];
+            uidv[g] = nuid[g];
+            hv[g] = nhv[g];
+        }
+    }
+    if (prev >= 0) store_rows();
+}
+
 // Any depth (TtLayers, tower_common.h).  Same gather (tt_hist_mean) and
 // re-normalisation as tt_user_kernel; the layers run from one packed
 // weight buffer (per layer W_l [w_l, in_l] row-major, then b_l [w_l]) read
@@ -283,6 +514,15 @@ constexpr size_t tt_user_lds(int dim, int h0, int h1) {
 }
 constexpr int TT_H0_MAX = 128;
 
+// tt_user_kernel_pass's: the same weights, then each wave's tile (2 KB at dim 32)
+constexpr size_t tt_pass_lds(int dim, int h0) {
+    const size_t h0p = (size_t)((h0 + 3) & ~3);
+    return sizeof(float) * ((size_t)h0 * (2 * dim + 4) + h0p + (size_t)dim * (h0p + 4) + dim +
+                            (size_t)4 * tt_pass_tile(dim));
+}
+// users per wave pass of the kernel nrk_tt_user_fwd runs at h0, 0 for tt_user_kernel
+static int tt_pass_users(int h0) { return h0 <= WAVE ? TT_PASS_G : 0; }
+
 extern "C" {
 
 int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* item_table,
@@ -301,9 +541,24 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
                 "null pointer");
     const size_t lds = tt_user_lds(dim, h0, h1);
     hipStream_t s = as_stream(stream);
-    // persistent grid of resident workgroups only (the weights' LDS admits ~5
-    // per CU): a grid larger than the resident set left the queued
+    // persistent grid of resident workgroups only (the weights' LDS admits 4 or
+    // 5 per CU): a grid larger than the resident set left the queued
     // workgroups to run after the first ones finished, on a thinner machine
+    if (tt_pass_users(h0)) {
+        const size_t plds = tt_pass_lds(dim, h0);
+        // at most one workgroup per 4 passes of TT_PASS_G users
+        const int64_t want = (n + 4 * TT_PASS_G - 1) / (4 * TT_PASS_G);
+        tt_for_dim(dim, [&](auto dc) {
+            constexpr int DD = decltype(dc)::value;
+            static_assert(tt_pass_lds(DD, WAVE) <= 65536, "tt_user_kernel_pass LDS: under the default limit");
+            const int grid = (int)std::max<int64_t>(
+                1, std::min(want, resident_blocks((const void*)tt_user_kernel_pass<DD>, 256, plds)));
+            tt_user_kernel_pass<DD><<<grid, 256, plds, s>>>(user_table, item_table, uid, hist, hist_len, n, seq_len, w0,
+                                                            b0, h0, w1, b1, out);
+        });
+        NRK_CHECK_LAUNCH();
+        return NRK_OK;
+    }
     tt_for_dim(dim, [&](auto dc) {
         constexpr int DD = decltype(dc)::value;
         constexpr size_t lds_max = tt_user_lds(DD, TT_H0_MAX, DD);  // h1 == dim
@@ -316,6 +571,16 @@ int nrk_tt_user_fwd(const float* user_table, int64_t n_user_rows, const float* i
     });
     NRK_CHECK_LAUNCH();
     return NRK_OK;
+}
+
+int nrk_tt_user_pass_users(int dim, int h0) {
+    clear_error();
+    if (tt_check_shape(__func__, dim)) return 0;
+    if (h0 < 1 || h0 > TT_H0_MAX) {
+        fail_as(__func__, NRK_EINVAL, "h0 must be in [1, 128]");
+        return 0;
+    }
+    return tt_pass_users(h0);
 }
 
 int nrk_tt_user_fwd_layers(const float* user_table, int64_t n_user_rows, const float* item_table,

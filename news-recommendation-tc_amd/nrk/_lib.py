@@ -27,6 +27,7 @@ SIGNATURES = {
     "nrk_last_error": (ctypes.c_char_p, []),
     "nrk_abi_version": (INT, []),
     "nrk_tt_user_fwd": (INT, [P, I64, P, I64, INT, P, P, P, I64, INT, P, P, INT, P, P, INT, P, P]),
+    "nrk_tt_user_pass_users": (INT, [INT, INT]),
     "nrk_tt_user_fwd_layers": (INT, [P, I64, P, I64, INT, P, P, P, I64, INT, P, INT, P, P, P]),
     "nrk_tt_item_fwd": (INT, [P, I64, INT, P, I64, P, P]),
     "nrk_tt_train_workspace_bytes": (SZ, [I64, I64, INT, INT, P, INT, INT]),

@@ -113,6 +113,17 @@ def tt_user_fwd(user_table, item_table, uid, hist, hist_len, w0, b0, w1, b1, val
     return out
 
 
+def tt_user_pass_users(d: int, h0: int) -> int:
+    """Users that one wave pass of tt_user_fwd's kernel handles together at
+    (d, h0), 0 where the one-user-per-wave kernel runs:
+    nrk_tt_user_pass_users (no device work)."""
+    L = _lib.lib()
+    g = L.nrk_tt_user_pass_users(int(d), int(h0))
+    if g == 0 and L.nrk_last_error():
+        raise ValueError(L.nrk_last_error().decode(errors="replace"))
+    return g
+
+
 def tt_user_fwd_layers(user_table, item_table, uid, hist, hist_len, layers):
     """The user tower at any depth (youtubednn_recaller.py:105-112):
     ``layers`` = [(W_l [w_l, in_l], b_l [w_l]), ...] fp32 device tensors, the
