@@ -39,14 +39,18 @@ def to_tensors(state, feats, dtype):
             for k in state_keys(feats, alphas=False)}
 
 
-def dice(x, eps=1e-8):
+def dice(x, eps=1e-8, stds=None):
     mean = x.mean(dim=0, keepdim=True)
     std = x.std(dim=0, keepdim=True)
+    if stds is not None:
+        stds.append(std.detach().reshape(-1).numpy())
     p = torch.sigmoid((x - mean) / (std + eps))
     return p * x + (1 - p) * 0.01 * x
 
 
-def probs_of(params, feats, batch):
+def probs_of(params, feats, batch, stds=None):
+    """``stds``: a list that receives the batch std of every Dice column (the
+    attention's, then the two MLP layers')."""
     uf, itf, cf = feats
     lin = torch.nn.functional.linear
     dtype = params["mlp.0.weight"].dtype
@@ -60,19 +64,34 @@ def probs_of(params, feats, batch):
           if cf else torch.zeros((B, 0), dtype=dtype))
     q = re.unsqueeze(1).expand(B, he.shape[1], re.shape[1])
     cat = torch.cat([he, q, q - he, q * he], dim=-1)
-    a = dice(lin(cat, params["activation_unit.mlp.0.weight"], params["activation_unit.mlp.0.bias"]))
+    a = dice(lin(cat, params["activation_unit.mlp.0.weight"], params["activation_unit.mlp.0.bias"]), stds=stds)
     w = lin(a, params["activation_unit.mlp.2.weight"], params["activation_unit.mlp.2.bias"])
     w = w * torch.as_tensor(np.asarray(batch["mask"]), dtype=dtype).unsqueeze(-1)
     wh = (w * he).sum(dim=1)
     x = torch.cat([ue, ce, re, wh], dim=1)
-    x = dice(lin(x, params["mlp.0.weight"], params["mlp.0.bias"]))
-    x = dice(lin(x, params["mlp.2.weight"], params["mlp.2.bias"]))
+    x = dice(lin(x, params["mlp.0.weight"], params["mlp.0.bias"]), stds=stds)
+    x = dice(lin(x, params["mlp.2.weight"], params["mlp.2.bias"]), stds=stds)
     return torch.sigmoid(lin(x, params["mlp.4.weight"], params["mlp.4.bias"])).squeeze(-1)
 
 
 def loss_of(params, feats, batch):
     p = probs_of(params, feats, batch)
     return torch.nn.BCELoss()(p, torch.as_tensor(np.asarray(batch["label"]), dtype=p.dtype))
+
+
+def min_dice_std(state, feats, batch, dtype=torch.float64):
+    """The smallest batch std over every Dice column of the forward: a column
+    with std exactly 0 is outside the trainer's contract (din_train.hip)."""
+    stds = []
+    with torch.no_grad():
+        probs_of(to_tensors(state, feats, dtype), feats, batch, stds)
+    return float(min(s.min() for s in stds))
+
+
+def loss_only(state, feats, batch, dtype=torch.float32):
+    """The forward alone: the loss as a float."""
+    with torch.no_grad():
+        return loss_of(to_tensors(state, feats, dtype), feats, batch).item()
 
 
 def grads(state, feats, batch, dtype=torch.float32):

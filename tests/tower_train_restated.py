@@ -116,6 +116,47 @@ def fixture_parts(g):
     return off, items, init, batches, int(g["seq_max_len"])
 
 
+def loss_only(state, off, items, batch, T, dtype=torch.float32, masks=None, p=0.0):
+    """The forward alone (no dense table gradients): the loss as a float."""
+    with torch.no_grad():
+        return loss_of(to_tensors(state, dtype), off, items, *batch, T, masks, p).item()
+
+
+def log_with_lengths(rng, lens, n_items):
+    """A click log whose row u has lens[u] clicks: (off int64 [U + 1], items int64)."""
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return off, rng.integers(0, n_items, off[-1]).astype(np.int64)
+
+
+def gathered_items(off, items, s_user, s_pos, T):
+    """Every history item a batch gathers, one entry per gather (repeats kept)."""
+    hist, hlen = histories(off, items, s_user, s_pos, T)
+    return hist[np.arange(T)[None, :] < hlen[:, None]]
+
+
+_GOLD = np.uint64(0x9E3779B97F4A7C15)
+
+
+def _mix(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def dropout_mask(seed, step, layer, batch, width, p):
+    """The trainer's counter-based keep mask [batch, width] (tower_train.hip:
+    splitmix64's finaliser over (seed, step, layer, sample), one draw per
+    unit, kept iff the draw's high word is >= p * 2^32), in numpy."""
+    if not p > 0:
+        return np.ones((batch, width), np.float32)
+    thr = np.uint64(max(1, int(min(float(np.float32(p)) * 4294967296.0, 4294967295.0))))
+    with np.errstate(over="ignore"):
+        k = _mix(np.array([seed % 2 ** 64], np.uint64) + _GOLD * np.uint64(step + 1))
+        key = _mix(k ^ ((np.uint64(layer) << np.uint64(32)) | np.arange(batch, dtype=np.uint64)))
+        draw = _mix(key[:, None] + _GOLD * (np.arange(width, dtype=np.uint64) + np.uint64(1))[None, :]) >> np.uint64(32)
+    return (draw >= thr).astype(np.float32)
+
+
 def err(a, ref64):
     """The measure every tolerance uses: max |a - ref| over the tensor."""
     return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(ref64, np.float64)))) if np.size(a) else 0.0
