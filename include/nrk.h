@@ -546,6 +546,31 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
                              float* out_probs, float* out_logits, void* workspace,
                              size_t workspace_bytes, nrk_stream_t stream);
 
+/* nrk_din_forward_segments for any DINModel the reference's RankConfig
+ * builds: n_layers in [1, 4] hidden layers (din_mlp_hidden_units,
+ * src/utils/config.py:117) of widths[n] in [1, 1024], widths[0] = h1, and
+ * activation 0 (Dice) or 1 (nn.PReLU(), din_activation, config.py:118,
+ * DIN.py:203-206).  Arguments as nrk_din_forward_segments up to mlp_b0, then
+ * HOST arrays of n_layers device pointers: mlp_w[n] / mlp_b[n] are the weight
+ * [widths[n + 1], widths[n]] and bias of hidden layer n + 2 for
+ * n < n_layers - 1, and mlp_w[n_layers - 1] [widths[n_layers - 1]] /
+ * mlp_b[n_layers - 1] [1] the output row.  slopes: DEVICE float [n_layers],
+ * the one slope of each PReLU (state_dict mlp.{2n+1}.weight); ignored (may be
+ * null) under Dice.  The attention unit is Dice under either activation
+ * (DIN.py:188), so the batch rules above hold for both.  Two Dice layers run
+ * exactly what nrk_din_forward_segments runs.  Other n_layers or widths:
+ * NRK_EUNSUPPORTED. */
+size_t nrk_din_mlp_workspace_bytes(int64_t n_samples, int64_t seg_len, int seq_len, int n_user, int n_item,
+                                   int n_ctx, int n_layers, const int* widths, int activation);
+int nrk_din_forward_mlp(const void* table, int table_dtype, const int64_t* row_base, int n_user, int n_item,
+                        int n_ctx, const int32_t* user_idx, const int32_t* item_idx, const int32_t* hist_idx,
+                        const int32_t* ctx_idx, const float* mask, int64_t n_samples, int64_t seg_len,
+                        int seq_len, const void* prep, const float* att_b0, const float* att_w1,
+                        const float* att_b1, const float* mlp_w0, const float* mlp_b0, int n_layers,
+                        const int* widths, const float* const* mlp_w, const float* const* mlp_b, int activation,
+                        const float* slopes, float* out_probs, float* out_logits, void* workspace,
+                        size_t workspace_bytes, nrk_stream_t stream);
+
 /* DIN training (DINRanker.train's loop body, src/rank/DIN.py:907-912): one
  * batch of DINModel.forward in train mode, mean BCELoss and the backward,
  * all fp32.  Table, row_base, index tensors and mask as nrk_din_forward;

@@ -30,6 +30,9 @@
 // din_att_out and runs the f32 MFMA din_gemm<false> instead of 3 and 4; the
 // second layer is din_gemm<true> instead of 6 on the general path and when
 // h2 > 128.
+// Steps 6 to 8 are the tail of a model with two Dice hidden layers.  Any
+// other depth (1 to 4) or the PReLU activation (nrk_din_forward_mlp) runs the
+// same steps 1 to 5 and then the kernels of din_tail.hip (din_run below).
 #include "din_common.h"
 
 #include <atomic>
@@ -715,12 +718,6 @@ static inline size_t din_tm_lds(int NI, int T) {
            + (size_t)TM_SW * 12 + (TM_TMAX + 4) * 4;  // perm, perm * T, perm * T * 144, c_t, counter
 }
 
-
-// Dice(x) with the batch (mean, 1 / (std + 1e-8)) of x's column (DIN.py:39-44)
-__device__ __forceinline__ float dice_fast(float x, float mean, float inv) {
-    const float p = __builtin_amdgcn_rcpf(1.0f + __expf((mean - x) * inv));
-    return p * x + ((1.0f - p) * 0.01f) * x;
-}
 
 // Plan of a run of TM_SW samples (one Dice batch):
 // n_b of every sample (1 + its last row that is not the collate's padding),
@@ -1548,7 +1545,7 @@ static inline size_t din_wh2_lds(int T, int NI) {
 // during step s and stored to the other LDS buffer after it (one barrier per
 // step); the A rows of step s+1 and the indices of step s+2 are in flight
 // during step s.  Per 64-row half: fp64 column sums for the next Dice.
-constexpr int MLP1_ROWS = 128;
+// (MLP1_ROWS = 128 rows per workgroup: din_common.h)
 
 template <int NT>
 __global__ void din_w1_pack_kernel(const float* __restrict__ W, int N, int K,
@@ -1896,6 +1893,11 @@ __global__ __launch_bounds__(256, 2) void din_mlp2_kernel(
 // A row and W row (two float4) -- the k order inside the chunk is permuted
 // identically for both operands.  Loads run two chunks ahead.
 // Writes per-row-block fp64 column sums (sum, sumsq) of C for the next Dice.
+// Copies to keep in step: din_tail.hip's tail_load / din_layer_kernel repeat
+// gemm_load / din_gemm_kernel with the activation as a template parameter, its
+// din_mlp2_prelu_kernel repeats din_mlp2_kernel above, and din_run's PReLU
+// fast path repeats the absmax + din_w1_pack launches of the Dice one (the
+// kernels here stay byte for byte what two-layer Dice models have always run).
 typedef float din_f16v __attribute__((ext_vector_type(16)));
 
 template <bool DICE_A>
@@ -2015,15 +2017,7 @@ __global__ __launch_bounds__(512) void din_gemm_kernel(
 // logit = sum_j w_j Dice(z2_j) + b (DIN.py:283-284), prob = sigmoid.  16
 // lanes per sample (4 samples per wave, lane l16 takes j = l16, l16 + 16, ...
 // in order), the 16 partial sums combined by a fixed DPP tree within the
-// row; grid-strided over the samples.
-__device__ __forceinline__ float row16_sum(float x) {
-    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1, 0xF, 0xF, false));   // quad_perm 1,0,3,2
-    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x4E, 0xF, 0xF, false));   // quad_perm 2,3,0,1
-    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x141, 0xF, 0xF, false));  // row_half_mirror
-    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x140, 0xF, 0xF, false));  // row_mirror
-    return x;
-}
-
+// row (row16_sum); grid-strided over the samples.
 __global__ __launch_bounds__(256) void din_head_kernel(const float* __restrict__ Z, const float2* __restrict__ zstats_all,
                                                        int64_t B, int64_t S, int H, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ probs,
@@ -2109,6 +2103,13 @@ struct DinWs {
     float* z2;
     double* z2part;
     float2* z2stats;
+    // layers 3 and 4 (din_tail.hip); zpart / zstats only under Dice
+    float* z3;
+    double* z3part;
+    float2* z3stats;
+    float* z4;
+    double* z4part;
+    float2* z4stats;
     size_t bytes;
 };
 
@@ -2124,16 +2125,21 @@ static inline int din_mlp1_nt(int h1) {
     return nt <= 4 ? 4 : nt <= 8 ? 8 : nt <= 13 ? 13 : 16;
 }
 
-// N samples in Dice batches (segments) of S
+// N samples in Dice batches (segments) of S; hidden widths h[0 .. L) of the
+// final MLP and its activation.  Two Dice layers give the layout this always
+// had; a PReLU tail reserves no partial or statistics buffer past z1's, and
+// the packed W1 only where din_mlp2 / din_mlp2_prelu run (L = 2).
 static DinWs din_ws_layout(void* base, int64_t N, int64_t S, int T, int n_user, int n_item, int n_ctx,
-                           int h1, int h2) {
-    DinWs w;
+                           int L, const int* h, int act) {
+    DinWs w = {};
     Arena a(base);
     const int64_t n_seg = (N + S - 1) / S;
     const int64_t nb_att = n_seg * std::max<int64_t>(din_att_groups(N, S), (S + TM_SW - 1) / TM_SW);
     const int64_t nb_m = (N + 63) / 64;
     const int IN = (n_user + n_ctx + 2 * n_item) * DIN_E;
+    const int h1 = h[0];
     const bool fast = din_fast(T, h1);
+    const bool dice = act == DIN_ACT_DICE;
     w.h = (float*)a.take((size_t)N * T * DIN_H * 4);
     w.hpart = (double*)a.take((size_t)nb_att * T * DIN_H * 16);
     w.plan = (int32_t*)a.take((size_t)n_seg * ((S + TM_SW - 1) / TM_SW) * TM_PLAN * 4);
@@ -2143,16 +2149,23 @@ static DinWs din_ws_layout(void* base, int64_t N, int64_t S, int T, int n_user, 
     w.hinv = fast ? (float2*)a.take((size_t)n_seg * T * DIN_H * 8) : nullptr;
     // [max |wh| per segment][max |W0|][max |z1| per segment][max |W1|]
     w.whmax = fast ? (unsigned int*)a.take((size_t)(2 * n_seg + 2) * 4) : nullptr;
-    w.w2pack = din_fast2(T, h1, h2)
-                   ? (din_half8*)a.take((size_t)((h1 + DIN_E - 1) / DIN_E) * din_mlp2_nt(h2) * 2048)
+    w.w2pack = L == 2 && din_fast2(T, h1, h[1])
+                   ? (din_half8*)a.take((size_t)((h1 + DIN_E - 1) / DIN_E) * din_mlp2_nt(h[1]) * 2048)
                    : nullptr;
     w.w1pack = fast ? (din_half8*)a.take((size_t)(IN / DIN_E) * din_mlp1_nt(h1) * 2048) : nullptr;
     w.z1 = (float*)a.take((size_t)N * h1 * 4);
     w.z1part = (double*)a.take((size_t)nb_m * h1 * 16);
     w.z1stats = (float2*)a.take((size_t)n_seg * h1 * 8);
-    w.z2 = (float*)a.take((size_t)N * h2 * 4);
-    w.z2part = (double*)a.take((size_t)nb_m * h2 * 16);
-    w.z2stats = (float2*)a.take((size_t)n_seg * h2 * 8);
+    float** zs[] = {&w.z2, &w.z3, &w.z4};
+    double** ps[] = {&w.z2part, &w.z3part, &w.z4part};
+    float2** ss[] = {&w.z2stats, &w.z3stats, &w.z4stats};
+    for (int n = 1; n < L; ++n) {
+        *zs[n - 1] = (float*)a.take((size_t)N * h[n] * 4);
+        if (dice) {
+            *ps[n - 1] = (double*)a.take((size_t)nb_m * h[n] * 16);
+            *ss[n - 1] = (float2*)a.take((size_t)n_seg * h[n] * 8);
+        }
+    }
     w.bytes = a.bytes;
     return w;
 }
@@ -2253,8 +2266,43 @@ size_t nrk_din_segments_workspace_bytes(int64_t n_samples, int64_t seg_len, int 
                                         int n_item, int n_ctx, int h1, int h2) {
     if (n_samples < 1 || seg_len < 1 || seq_len < 1) return 0;
     if (seg_len > n_samples) seg_len = n_samples;
-    return din_ws_layout(nullptr, n_samples, seg_len, seq_len, n_user, n_item, n_ctx, h1, h2).bytes;
+    const int h[2] = {h1, h2};
+    return din_ws_layout(nullptr, n_samples, seg_len, seq_len, n_user, n_item, n_ctx, 2, h, DIN_ACT_DICE).bytes;
 }
+
+size_t nrk_din_mlp_workspace_bytes(int64_t n_samples, int64_t seg_len, int seq_len, int n_user, int n_item,
+                                   int n_ctx, int n_layers, const int* widths, int activation) {
+    if (n_samples < 1 || seg_len < 1 || seq_len < 1 || !widths || n_layers < 1 || n_layers > DIN_MAX_LAYERS) return 0;
+    if (activation != DIN_ACT_DICE && activation != DIN_ACT_PRELU) return 0;
+    for (int n = 0; n < n_layers; ++n)
+        if (widths[n] < 1 || widths[n] > 1024) return 0;
+    if (seg_len > n_samples) seg_len = n_samples;
+    return din_ws_layout(nullptr, n_samples, seg_len, seq_len, n_user, n_item, n_ctx, n_layers, widths, activation)
+        .bytes;
+}
+
+// One forward call after its entry point's checks: the arguments of
+// nrk_din_forward_mlp, the legacy entries' two layers restated in its terms.
+struct DinCall {
+    const void* table;
+    int table_dtype;
+    const int64_t* row_base;
+    int n_user, n_item, n_ctx;
+    const int32_t *user_idx, *item_idx, *hist_idx, *ctx_idx;
+    const float* mask;
+    int64_t batch, S;
+    int T;
+    const void* prep;
+    const float *att_b0, *att_w1, *att_b1, *mlp_w0, *mlp_b0;
+    int L;                             // hidden layers
+    int h[DIN_MAX_LAYERS];             // their widths
+    const float* mw[DIN_MAX_LAYERS];   // weights of layers 2..L, then the output row
+    const float* mb[DIN_MAX_LAYERS];   // their biases
+    int act;
+    const float* slopes;               // device [L], PReLU only
+    float *out_probs, *out_logits;
+};
+static int din_run(const char* fn, const DinCall& c, const DinWs& w, hipStream_t s);
 
 size_t nrk_din_workspace_bytes(int64_t batch, int seq_len, int n_user, int n_item, int n_ctx,
                                int h1, int h2) {
@@ -2290,14 +2338,79 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
                 "null pointer");
     NRK_REQUIRE(n_ctx == 0 || ctx_idx, "ctx_idx null");
     NRK_REQUIRE(n_seg < (1ll << 31) && batch < (1ll << 40), "too many samples");
-    const DinWs w = din_ws_layout(workspace, batch, S, seq_len, n_user, n_item, n_ctx, h1, h2);
+    const int h[2] = {h1, h2};
+    const DinWs w = din_ws_layout(workspace, batch, S, seq_len, n_user, n_item, n_ctx, 2, h, DIN_ACT_DICE);
     NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
-    hipStream_t s = as_stream(stream);
-    const int T = seq_len;
+    NRK_REQUIRE(n_seg * din_att_groups(batch, S) < (1ll << 31), "too many segments");
+    const DinCall c = {table, table_dtype, row_base, n_user, n_item, n_ctx, user_idx, item_idx, hist_idx, ctx_idx,
+                       mask, batch, S, seq_len, prep, att_b0, att_w1, att_b1, mlp_w0, mlp_b0, 2, {h1, h2},
+                       {mlp_w1, mlp_w2}, {mlp_b1, mlp_b2}, DIN_ACT_DICE, nullptr, out_probs, out_logits};
+    return din_run(__func__, c, w, as_stream(stream));
+}
+
+int nrk_din_forward_mlp(const void* table, int table_dtype, const int64_t* row_base, int n_user, int n_item,
+                        int n_ctx, const int32_t* user_idx, const int32_t* item_idx, const int32_t* hist_idx,
+                        const int32_t* ctx_idx, const float* mask, int64_t n_samples, int64_t seg_len,
+                        int seq_len, const void* prep, const float* att_b0, const float* att_w1,
+                        const float* att_b1, const float* mlp_w0, const float* mlp_b0, int n_layers,
+                        const int* widths, const float* const* mlp_w, const float* const* mlp_b, int activation,
+                        const float* slopes, float* out_probs, float* out_logits, void* workspace,
+                        size_t workspace_bytes, nrk_stream_t stream) {
+    clear_error();
+    NRK_REQUIRE(table_dtype == 0 || table_dtype == 1, "table_dtype must be 0 (f32) or 1 (bf16)");
+    NRK_REQUIRE(n_samples >= 1 && seg_len >= 1, "n_samples and seg_len must be >= 1");
+    const int64_t batch = n_samples;
+    const int64_t S = seg_len < n_samples ? seg_len : n_samples;
+    const int64_t n_seg = (batch + S - 1) / S;
+    // the attention unit is Dice under either activation (DIN.py:188)
+    if (n_seg == 1)
+        NRK_REQUIRE(batch >= 2, "batch must be >= 2 (Dice uses the batch std; B = 1 is NaN in the reference)");
+    else
+        NRK_REQUIRE(S % 64 == 0, "seg_len must be a multiple of 64 when the samples span several segments");
+    NRK_REQUIRE(seq_len >= 1 && seq_len <= 128, "seq_len must be in [1, 128]");
+    NRK_REQUIRE(n_user >= 1 && n_ctx >= 0 && n_item >= 1, "bad feature counts");
+    if (const int e = din_check_n_item(__func__, n_item)) return e;
+    if (n_layers < 1 || n_layers > DIN_MAX_LAYERS) NRK_UNSUPPORTED("n_layers must be in [1, 4]");
+    NRK_REQUIRE(activation == DIN_ACT_DICE || activation == DIN_ACT_PRELU,
+                "activation must be 0 (dice) or 1 (prelu)");
+    NRK_REQUIRE(widths && mlp_w && mlp_b, "null pointer (widths, mlp_w or mlp_b)");
+    for (int n = 0; n < n_layers; ++n) {
+        if (widths[n] < 1 || widths[n] > 1024) NRK_UNSUPPORTED("hidden widths must be in [1, 1024]");
+        NRK_REQUIRE(mlp_w[n] && mlp_b[n], "null pointer in mlp_w / mlp_b");
+    }
+    NRK_REQUIRE(activation != DIN_ACT_PRELU || slopes, "slopes null under prelu");
+    NRK_REQUIRE(table && row_base && user_idx && item_idx && hist_idx && mask && prep && att_b0 && att_w1 &&
+                    att_b1 && mlp_w0 && mlp_b0 && out_probs && workspace,
+                "null pointer");
+    NRK_REQUIRE(n_ctx == 0 || ctx_idx, "ctx_idx null");
+    NRK_REQUIRE(n_seg < (1ll << 31) && batch < (1ll << 40), "too many samples");
+    const DinWs w = din_ws_layout(workspace, batch, S, seq_len, n_user, n_item, n_ctx, n_layers, widths, activation);
+    NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small");
+    NRK_REQUIRE(n_seg * din_att_groups(batch, S) < (1ll << 31), "too many segments");
+    DinCall c = {table, table_dtype, row_base, n_user, n_item, n_ctx, user_idx, item_idx, hist_idx, ctx_idx,
+                 mask, batch, S, seq_len, prep, att_b0, att_w1, att_b1, mlp_w0, mlp_b0, n_layers, {}, {}, {},
+                 activation, slopes, out_probs, out_logits};
+    for (int n = 0; n < n_layers; ++n) {
+        c.h[n] = widths[n];
+        c.mw[n] = mlp_w[n];
+        c.mb[n] = mlp_b[n];
+    }
+    return din_run(__func__, c, w, as_stream(stream));
+}
+
+static int din_run(const char* fn, const DinCall& c, const DinWs& w, hipStream_t s) {
+    const void* table = c.table;
+    const int table_dtype = c.table_dtype, n_user = c.n_user, n_item = c.n_item, n_ctx = c.n_ctx, T = c.T;
+    const int64_t* row_base = c.row_base;
+    const int32_t *user_idx = c.user_idx, *item_idx = c.item_idx, *hist_idx = c.hist_idx, *ctx_idx = c.ctx_idx;
+    const float *mask = c.mask, *att_b0 = c.att_b0, *att_w1 = c.att_w1, *att_b1 = c.att_b1, *mlp_w0 = c.mlp_w0,
+                *mlp_b0 = c.mlp_b0;
+    const void* prep = c.prep;
+    const int64_t batch = c.batch, S = c.S, n_seg = (batch + S - 1) / S;
+    const int h1 = c.h[0];
     const int IN = (n_user + n_ctx + 2 * n_item) * DIN_E;
     const int G = din_att_groups(batch, S);
     const int64_t nb_att = n_seg * G;
-    NRK_REQUIRE(nb_att < (1ll << 31), "too many segments");
     const float* pf = reinterpret_cast<const float*>(prep);
     // position-major attention (bf16 tables, T <= 64, <= 4 item features,
     // the fast MLP path): plan, then h + its statistics
@@ -2389,6 +2502,45 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
     }
     col_stats_kernel<<<dim3(gs, (h1 + 3) / 4), 256, 0, s>>>(w.z1part, bps, (int)nb_m, h1, batch, S,
                                                             nullptr, w.z1stats);
+    auto launched = [&]() {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? NRK_OK : fail_as(fn, NRK_EHIP, hipGetErrorString(e));
+    };
+    if (c.L != 2 || c.act != DIN_ACT_DICE) {
+        // the tail of din_tail.hip: layers 2..L with the activation on load, a
+        // col_stats pass behind each Dice layer only, then the head
+        float* const zs[] = {w.z1, w.z2, w.z3, w.z4};
+        double* const ps[] = {w.z1part, w.z2part, w.z3part, w.z4part};
+        float2* const ss[] = {w.z1stats, w.z2stats, w.z3stats, w.z4stats};
+        for (int n = 1; n < c.L; ++n) {
+            const int K = c.h[n - 1], N = c.h[n];
+            if (c.L == 2 && c.act == DIN_ACT_PRELU && din_fast2(T, K, N)) {
+                unsigned int* z1max = w.whmax + n_seg + 1;
+                unsigned int* w2max = z1max + n_seg;
+                const int64_t nw = (int64_t)N * K;
+                din_absmax_kernel<<<grid_for(nw, 256, 64), 256, 0, s>>>(c.mw[0], 0, nw, w2max);
+                const int NT2 = din_mlp2_nt(N);
+                const unsigned gp = grid_for((int64_t)((K + DIN_E - 1) / DIN_E) * NT2 * 64, 256, 512);
+                with_rung<2, 4, 5, 8>(NT2, [&](auto nt) {
+                    din_w1_pack_kernel<decltype(nt)::value><<<gp, 256, 0, s>>>(c.mw[0], N, K, w2max, w.w2pack);
+                });
+                din_tail_mlp2_prelu(NT2, w.z1, c.slopes, z1max, w2max, reinterpret_cast<const din_u4*>(w.w2pack),
+                                    c.mb[0], batch, S, K, N, w.z2, s);
+            } else {
+                din_tail_layer(c.act, zs[n - 1], ss[n - 1], c.slopes ? c.slopes + (n - 1) : nullptr, c.mw[n - 1],
+                               c.mb[n - 1], batch, S, N, K, zs[n], ps[n], s);
+            }
+            if (c.act == DIN_ACT_DICE)
+                col_stats_kernel<<<dim3(gs, (N + 3) / 4), 256, 0, s>>>(ps[n], bps, (int)nb_m, N, batch, S, nullptr,
+                                                                       ss[n]);
+        }
+        din_tail_head(c.act, zs[c.L - 1], ss[c.L - 1], c.slopes ? c.slopes + (c.L - 1) : nullptr, batch, S,
+                      c.h[c.L - 1], c.mw[c.L - 1], c.mb[c.L - 1], c.out_probs, c.out_logits, s);
+        return launched();
+    }
+    const int h2 = c.h[1];
+    const float *mlp_w1 = c.mw[0], *mlp_b1 = c.mb[0], *mlp_w2 = c.mw[1], *mlp_b2 = c.mb[1];
+    float *out_probs = c.out_probs, *out_logits = c.out_logits;
     if (din_fast2(T, h1, h2)) {
         unsigned int* z1max = w.whmax + n_seg + 1;
         unsigned int* w2max = z1max + n_seg;
@@ -2417,8 +2569,7 @@ int nrk_din_forward_segments(const void* table, int table_dtype, const int64_t* 
                                                             nullptr, w.z2stats);
     din_head_kernel<<<grid_for(batch, 16, 8192), 256, 0, s>>>(
         w.z2, w.z2stats, batch, S, h2, mlp_w2, mlp_b2, out_probs, out_logits);
-    NRK_CHECK_LAUNCH();
-    return NRK_OK;
+    return launched();
 }
 
 int nrk_din_forward(const void* table, int table_dtype, const int64_t* row_base, int n_user,

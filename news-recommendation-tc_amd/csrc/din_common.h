@@ -38,6 +38,43 @@ __device__ __forceinline__ void split8(const float (&x)[8], float s, din_half8& 
     }
 }
 
+// Dice(x) with the batch (mean, 1 / (std + 1e-8)) of x's column (DIN.py:39-44)
+__device__ __forceinline__ float dice_fast(float x, float mean, float inv) {
+    const float p = __builtin_amdgcn_rcpf(1.0f + __expf((mean - x) * inv));
+    return p * x + ((1.0f - p) * 0.01f) * x;
+}
+
+// sum over the 16 lanes of a DPP row, the same fixed tree in every lane
+__device__ __forceinline__ float row16_sum(float x) {
+    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1, 0xF, 0xF, false));   // quad_perm 1,0,3,2
+    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x4E, 0xF, 0xF, false));   // quad_perm 2,3,0,1
+    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x141, 0xF, 0xF, false));  // row_half_mirror
+    x += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x140, 0xF, 0xF, false));  // row_mirror
+    return x;
+}
+
+constexpr int MLP1_ROWS = 128;  // rows per workgroup of din_mlp1 / din_mlp2 (4 waves x 32)
+
+// ------------------------------------------------- MLP tail (din_tail.hip) --
+// The final MLP past z1 for 1 to 4 hidden layers and either activation
+// (DIN.py:203-206): host launchers, dispatched by din.hip.  `slope` points at
+// the consuming activation's PReLU slope on the device (unused under Dice,
+// like `stats` under PReLU).
+constexpr int DIN_ACT_DICE = 0, DIN_ACT_PRELU = 1;
+constexpr int DIN_MAX_LAYERS = 4;
+// C[M][N] = act(A)[M][K] W[N][K]^T + bias; Dice also writes the per-64-row fp64
+// column partials of C (for col_stats), PReLU leaves `partial` untouched
+void din_tail_layer(int act, const float* A, const float2* stats, const float* slope, const float* W,
+                    const float* bias, int64_t M, int64_t S, int N, int K, float* C, double* partial,
+                    hipStream_t s);
+// the same product on the packed split-fp16 path of din_mlp2 (K <= 256, N <= 128), PReLU on load
+void din_tail_mlp2_prelu(int nt, const float* A, const float* slope, const unsigned int* amax,
+                         const unsigned int* wmax, const din_u4* wpack, const float* bias, int64_t M, int64_t S,
+                         int K, int N, float* C, hipStream_t s);
+// logit = w . act(Z) + b, prob = sigmoid(logit)
+void din_tail_head(int act, const float* Z, const float2* stats, const float* slope, int64_t B, int64_t S, int H,
+                   const float* w, const float* bias, float* probs, float* logits, hipStream_t s);
+
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS traffic
 // (lgkmcnt) but not for its outstanding global loads, which __syncthreads()
 // (a workgroup release fence: vmcnt(0) on gfx9) would drain -- prefetched

@@ -112,6 +112,9 @@ SIGNATURES = {
     "nrk_din_segments_workspace_bytes": (SZ, [I64, I64, INT, INT, INT, INT, INT, INT]),
     "nrk_din_forward_segments": (INT, [P, INT, P, INT, INT, INT, P, P, P, P, P, I64, I64, INT, P, P,
                                        P, P, P, P, INT, P, P, INT, P, P, P, P, P, SZ, P]),
+    "nrk_din_mlp_workspace_bytes": (SZ, [I64, I64, INT, INT, INT, INT, INT, P, INT]),
+    "nrk_din_forward_mlp": (INT, [P, INT, P, INT, INT, INT, P, P, P, P, P, I64, I64, INT, P, P, P, P, P, P,
+                                  INT, P, P, P, INT, P, P, P, P, SZ, P]),
     "nrk_din_train_workspace_bytes": (SZ, [I64, INT, INT, INT, INT, INT, INT, INT, INT, I64, INT]),
     "nrk_din_train_grad": (INT, [P, I64, INT, INT, P, INT, INT, INT, P, INT, INT, INT, P, P, P, P, P, P, I64, INT,
                                  P, P, P, P, P, P, SZ, P]),

@@ -6,6 +6,8 @@ allocates its outputs and workspace with the torch caching allocator.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -644,6 +646,8 @@ def row_normalize(x, norms=False):
 
 # -------------------------------------------------------------------- DIN --
 DIN_KERNEL_ITEM_FEATS = (1, 2, 4, 8)  # item-feature counts the attention kernels are instantiated for
+DIN_MAX_LAYERS = 4  # hidden layers of the final MLP (csrc/din_tail.hip); widths up to 1024
+DIN_ACTIVATIONS = ("dice", "prelu")  # din_activation (config.py:118): nrk_din_forward_mlp's codes 0, 1
 
 
 class DinParams:
@@ -660,7 +664,13 @@ class DinParams:
     with a shared all-zero row up to 1, 2, 4 or 8 -- every extra product is
     an exact 0, so the results are those of the D-wide model.  ``n_user`` /
     ``n_item`` / ``n_ctx`` / ``vocab`` describe the caller's features;
-    ``kn_*`` the kernel's (include/nrk.h, nrk_din_remap_index)."""
+    ``kn_*`` the kernel's (include/nrk.h, nrk_din_remap_index).
+
+    The final MLP is read off the state_dict: ``widths`` (1 to 4 hidden
+    layers, ``din_mlp_hidden_units``), ``activation`` ("dice" or "prelu",
+    ``din_activation``) and, under PReLU, ``slopes`` (device float32 [L], one
+    per layer).  Two-layer models also expose ``h2`` / ``mlp_w1`` / ``mlp_b1``
+    / ``mlp_w2`` / ``mlp_b2``."""
 
     def __init__(self, state_dict, user_feats, item_feats, ctx_feats, table_dtype="fp32",
                  device="cuda"):
@@ -758,15 +768,56 @@ class DinParams:
         self.att_w1 = d(arr("activation_unit.mlp.2.weight").reshape(-1))
         self.att_b1 = d(arr("activation_unit.mlp.2.bias"))
         self.mlp_b0 = d(arr("mlp.0.bias"))
-        self.mlp_w1, self.mlp_b1 = d(arr("mlp.2.weight")), d(arr("mlp.2.bias"))
-        self.mlp_w2 = d(arr("mlp.4.weight").reshape(-1))
-        self.mlp_b2 = d(arr("mlp.4.bias"))
-        for name in ("att_w0", "att_b0", "att_w1", "att_b1", "mlp_w0", "mlp_b0", "mlp_w1", "mlp_b1", "mlp_w2",
-                     "mlp_b2"):
-            _finite(getattr(self, name), f"DIN weight {name}")
-        self.h1, self.h2 = self.mlp_w0.shape[0], self.mlp_w1.shape[0]
-        if self.mlp_w1.shape[1] != self.h1 or self.mlp_w2.numel() != self.h2 or self.att_w1.numel() != 36:
+        # the final MLP (DIN.py:196-212): Linear mlp.{2n} per hidden layer n < L with its
+        # activation at mlp.{2n+1} (Dice: an unused ``alpha``; nn.PReLU(): ``weight`` (1,)),
+        # then the one-row Linear mlp.{2L}
+        L = 0
+        while f"mlp.{2 * L}.weight" in state_dict:
+            L += 1
+        L -= 1
+        if L < 1 or L > DIN_MAX_LAYERS:
+            raise NotImplementedError(f"the DIN kernels implement 1 to {DIN_MAX_LAYERS} MLP hidden layers, "
+                                      f"the state_dict has {L}")
+        kinds = {"prelu" if f"mlp.{2 * n + 1}.weight" in state_dict else "dice" for n in range(L)}
+        if any(f"mlp.{2 * n + 1}.weight" in state_dict and f"mlp.{2 * n + 1}.alpha" in state_dict
+               for n in range(L)) or len(kinds) != 1:
+            raise ValueError("the MLP's activations mix Dice (alpha) and PReLU (weight) layers")
+        self.activation = kinds.pop()
+        ws = [w0] + [arr(f"mlp.{2 * n}.weight") for n in range(1, L + 1)]
+        bs = [arr(f"mlp.{2 * n}.bias") for n in range(L + 1)]
+        self.widths = [int(w.shape[0]) for w in ws[:L]]
+        for n in range(1, L + 1):
+            if ws[n].ndim != 2 or ws[n].shape[1] != self.widths[n - 1] or bs[n].shape != (ws[n].shape[0],):
+                raise ValueError("state_dict shapes do not match the feature lists")
+        if ws[L].shape[0] != 1 or bs[0].shape != (self.widths[0],) or min(self.widths) < 1:
             raise ValueError("state_dict shapes do not match the feature lists")
+        if max(self.widths) > 1024:
+            raise NotImplementedError("the DIN kernels implement MLP widths up to 1024")
+        self.mlp_ws = [d(w) for w in ws[1:L]] + [d(ws[L].reshape(-1))]  # layers 2..L, then the output row
+        self.mlp_bs = [d(b) for b in bs[1:]]
+        if self.activation == "prelu":
+            sl = [arr(f"mlp.{2 * n + 1}.weight") for n in range(L)]
+            if any(a.shape != (1,) for a in sl):
+                raise NotImplementedError("nn.PReLU() with one slope per layer only (mlp.{2n+1}.weight of shape (1,))")
+            self.slopes = d(np.concatenate(sl))
+            _finite(self.slopes, "DIN PReLU slopes")
+        else:
+            self.slopes = None
+        for name in ("att_w0", "att_b0", "att_w1", "att_b1", "mlp_w0", "mlp_b0"):
+            _finite(getattr(self, name), f"DIN weight {name}")
+        for n, t in enumerate(self.mlp_ws + self.mlp_bs):
+            _finite(t, f"DIN weight mlp.{2 * (n % L + 1)}")
+        if self.att_w1.numel() != 36:
+            raise ValueError("state_dict shapes do not match the feature lists")
+        self.h1 = self.widths[0]
+        if L == 2:  # what two-layer callers have always read
+            self.h2 = self.widths[1]
+            self.mlp_w1, self.mlp_b1 = self.mlp_ws[0], self.mlp_bs[0]
+            self.mlp_w2, self.mlp_b2 = self.mlp_ws[1], self.mlp_bs[1]
+        # host arrays of nrk_din_forward_mlp (kept alive with the tensors they point to)
+        self._c_widths = (ctypes.c_int * L)(*self.widths)
+        self._c_w = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.mlp_ws])
+        self._c_b = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.mlp_bs])
         nb = _lib.lib().nrk_din_prep_bytes(self.kn_item, self.table.shape[0])
         self.prep = torch.empty(nb, dtype=torch.uint8, device=device)
         _lib.call("nrk_din_prepare", _ptr(self.att_w0), self.kn_item, _ptr(self.table), self.table_code,
@@ -812,6 +863,19 @@ def _din_seg(B, batch_size):
     return S
 
 
+def _din_two_dice(p):
+    """Two Dice hidden layers: the shape nrk_din_forward_segments serves."""
+    return len(p.widths) == 2 and p.activation == "dice"
+
+
+def _din_workspace_bytes(p, B, S, T):
+    L = _lib.lib()
+    if _din_two_dice(p):
+        return L.nrk_din_segments_workspace_bytes(B, S, T, p.kn_user, p.kn_item, p.kn_ctx, p.h1, p.h2)
+    return L.nrk_din_mlp_workspace_bytes(B, S, T, p.kn_user, p.kn_item, p.kn_ctx, len(p.widths),
+                                         ctypes.cast(p._c_widths, _P), DIN_ACTIVATIONS.index(p.activation))
+
+
 def din_forward(p: DinParams, user, item, hist, ctx, mask, logits=False, workspace=None,
                 out=None, validate=True, batch_size=None):
     """DIN scores of B samples: int32 index tensors user [B,Fu], item [B,Fi],
@@ -840,14 +904,22 @@ def din_forward(p: DinParams, user, item, hist, ctx, mask, logits=False, workspa
     else:
         probs = torch.empty(B, dtype=torch.float32, device=mask.device)
     lg = torch.empty(B, dtype=torch.float32, device=mask.device) if logits else None
-    nb = _lib.lib().nrk_din_segments_workspace_bytes(B, S, T, p.kn_user, p.kn_item, p.kn_ctx, p.h1, p.h2)
+    nb = _din_workspace_bytes(p, B, S, T)
     if workspace is None or workspace.numel() < nb:
         workspace = torch.empty(nb, dtype=torch.uint8, device=mask.device)
-    _lib.call("nrk_din_forward_segments", _ptr(p.table), p.table_code, _ptr(p.row_base), p.kn_user,
-              p.kn_item, p.kn_ctx, _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx), _ptr(mask), B, S, T,
-              _ptr(p.prep), _ptr(p.att_b0), _ptr(p.att_w1), _ptr(p.att_b1), _ptr(p.mlp_w0),
-              _ptr(p.mlp_b0), p.h1, _ptr(p.mlp_w1), _ptr(p.mlp_b1), p.h2, _ptr(p.mlp_w2),
-              _ptr(p.mlp_b2), _ptr(probs), _ptr(lg), _ptr(workspace), workspace.numel(), _stream())
+    if _din_two_dice(p):
+        _lib.call("nrk_din_forward_segments", _ptr(p.table), p.table_code, _ptr(p.row_base), p.kn_user,
+                  p.kn_item, p.kn_ctx, _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx), _ptr(mask), B, S, T,
+                  _ptr(p.prep), _ptr(p.att_b0), _ptr(p.att_w1), _ptr(p.att_b1), _ptr(p.mlp_w0),
+                  _ptr(p.mlp_b0), p.h1, _ptr(p.mlp_w1), _ptr(p.mlp_b1), p.h2, _ptr(p.mlp_w2),
+                  _ptr(p.mlp_b2), _ptr(probs), _ptr(lg), _ptr(workspace), workspace.numel(), _stream())
+    else:  # other depths, PReLU: the general entry (csrc/din_tail.hip behind the same front)
+        _lib.call("nrk_din_forward_mlp", _ptr(p.table), p.table_code, _ptr(p.row_base), p.kn_user,
+                  p.kn_item, p.kn_ctx, _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx), _ptr(mask), B, S, T,
+                  _ptr(p.prep), _ptr(p.att_b0), _ptr(p.att_w1), _ptr(p.att_b1), _ptr(p.mlp_w0),
+                  _ptr(p.mlp_b0), len(p.widths), ctypes.cast(p._c_widths, _P), ctypes.cast(p._c_w, _P),
+                  ctypes.cast(p._c_b, _P), DIN_ACTIVATIONS.index(p.activation), _ptr(p.slopes), _ptr(probs),
+                  _ptr(lg), _ptr(workspace), workspace.numel(), _stream())
     if S < B and B % S == 1:  # trailing batch of one row: std undefined -> NaN (reference)
         probs[B - 1] = float("nan")
         if lg is not None:
@@ -857,8 +929,7 @@ def din_forward(p: DinParams, user, item, hist, ctx, mask, logits=False, workspa
 
 def din_workspace(p: DinParams, B, T, device, batch_size=None):
     S = _din_seg(B, batch_size)
-    nb = _lib.lib().nrk_din_segments_workspace_bytes(B, S, T, p.kn_user, p.kn_item, p.kn_ctx, p.h1, p.h2)
-    return torch.empty(nb, dtype=torch.uint8, device=device)
+    return torch.empty(_din_workspace_bytes(p, B, S, T), dtype=torch.uint8, device=device)
 
 
 # ----------------------------------------------------------- DIN training --

@@ -93,10 +93,12 @@ class DINScorer:
         return out
 
 
-def _expected_state(uv, iv, cv, dim, mlp_hidden):
-    """key -> shape of DINModel(uv, iv, cv, dim, [36], mlp_hidden, "dice")'s
+def _expected_state(uv, iv, cv, dim, mlp_hidden, activation="dice"):
+    """key -> shape of DINModel(uv, iv, cv, dim, [36], mlp_hidden, activation)'s
     state_dict (DIN.py:133-212; ActivationUnit is built with its defaults,
-    :188; each Dice holds an unused ``alpha``)."""
+    :188, so it is Dice under either activation; each Dice holds an unused
+    ``alpha``, each nn.PReLU() of the final MLP its one slope ``weight``,
+    :203-206)."""
     exp = {}
     for grp, vocab in (("user_profile_embedding_dict", uv), ("item_embedding_dict", iv),
                        ("context_embedding_dict", cv)):
@@ -109,7 +111,10 @@ def _expected_state(uv, iv, cv, dim, mlp_hidden):
     cur = (len(uv) + len(cv)) * dim + 2 * item_dim
     for n, unit in enumerate(mlp_hidden):
         exp[f"mlp.{2 * n}.weight"], exp[f"mlp.{2 * n}.bias"] = (unit, cur), (unit,)
-        exp[f"mlp.{2 * n + 1}.alpha"] = ()
+        if activation == "prelu":
+            exp[f"mlp.{2 * n + 1}.weight"] = (1,)
+        else:
+            exp[f"mlp.{2 * n + 1}.alpha"] = ()
         cur = unit
     exp[f"mlp.{2 * len(mlp_hidden)}.weight"], exp[f"mlp.{2 * len(mlp_hidden)}.bias"] = (1, cur), (1,)
     return exp
@@ -261,16 +266,19 @@ class DINRanker(BaseRanker):
         encoders_path = os.path.join(load_dir, "label_encoders.pkl")
         self.label_encoders = load_pickle(encoders_path) if os.path.exists(encoders_path) else {}
         uv, iv, cv = self._prepare_vocab_dicts()
-        if metadata.get("din_activation", "dice") != "dice":
-            raise NotImplementedError("the DIN kernels implement the Dice activation only")
+        activation = metadata.get("din_activation", "dice")
+        if activation not in ops.DIN_ACTIVATIONS:
+            raise NotImplementedError(f"the DIN kernels implement din_activation 'dice' and 'prelu', "
+                                      f"got {activation!r}")
         hidden = list(metadata.get("din_mlp_hidden_units", [200, 80]))
-        if len(hidden) != 2:
-            raise NotImplementedError("the DIN kernels implement two MLP hidden layers")
+        if not 1 <= len(hidden) <= ops.DIN_MAX_LAYERS or not all(1 <= int(u) <= 1024 for u in hidden):
+            raise NotImplementedError(f"the DIN kernels implement 1 to {ops.DIN_MAX_LAYERS} MLP hidden layers of "
+                                      f"width 1 to 1024, got din_mlp_hidden_units = {hidden}")
         model_path = os.path.join(load_dir, "din_model.pth")
         if not os.path.exists(model_path):
             raise FileNotFoundError(f"Model weights not found at: {model_path}")
         sd = torch.load(model_path, map_location="cpu", weights_only=True)
-        exp = _expected_state(uv, iv, cv, int(metadata["din_embedding_dim"]), hidden)
+        exp = _expected_state(uv, iv, cv, int(metadata["din_embedding_dim"]), hidden, activation)
         missing, unexpected = sorted(set(exp) - set(sd)), sorted(set(sd) - set(exp))
         bad = [k for k in exp if k in sd and tuple(sd[k].shape) != exp[k]]
         if missing or unexpected or bad:  # load_state_dict(strict=True) refuses these
@@ -433,7 +441,9 @@ class DINRanker(BaseRanker):
             val_data = self._apply_negative_sampling(val_data, cfg.negative_positive_ratio, "Validation Set")
         uv, iv, cv = self._prepare_vocab_dicts()
         if cfg.din_activation != "dice" or len(cfg.din_mlp_hidden_units) != 2:
-            raise NotImplementedError("DIN training implements Dice and two MLP hidden layers")
+            raise NotImplementedError("DIN training implements Dice and two MLP hidden layers; a model of another "
+                                      "depth or with PReLU, trained elsewhere, can be loaded (load_model) and "
+                                      "scored (predict)")
         self.user_profile_features, self.item_features, self.context_features = list(uv), list(iv), list(cv)
         self.encoder = DinEncoder(self.user_profile_dict, self.item_features_dict, self.user_history_dict,
                                   self.user_profile_features, self.item_features, self.context_features,
