@@ -601,6 +601,37 @@ int nrk_din_train_grad(const float* table, int64_t n_table_rows, int dim, int ta
                        float* loss, float* w_grad, int32_t* t_rows, float* t_vals, int32_t* t_count, void* workspace,
                        size_t workspace_bytes, nrk_stream_t stream);
 
+/* nrk_din_train_grad for every DINModel nrk_din_forward_mlp serves: n_layers
+ * in [1, 4] hidden layers of widths[n] in [1, 1024] (HOST array) and
+ * activation 0 (Dice) or 1 (nn.PReLU(): one trained slope per layer,
+ * initialised to 0.25 by torch).  Everything else as nrk_din_train_grad, the
+ * attention unit (Dice, hidden width 36) and the batch rule included: batch
+ * in [2, 8192] under either activation.  Packed weights and w_grad:
+ *   att_w0 | att_b0 | att_w1 | att_b1 |
+ *   per hidden layer n: w_n [widths[n], k_n] | b_n [widths[n]] |
+ *                       (PReLU only) slope_n [1] |         k_0 = in, k_n = widths[n-1]
+ *   w_out [widths[n_layers-1]] | b_out [1]
+ * nrk_din_train_mlp_n_weights is that vector's length (0 and the last error
+ * if the shape is refused).  Two Dice layers give nrk_din_train_grad's layout
+ * and run the same device code: the results are bit-equal.  nrk_din_adam_step
+ * takes the longer vector as it is; the slopes get their update from the same
+ * sweep.  PReLU follows torch at the kink: y = x > 0 ? x : a x,
+ * dx = x > 0 ? g : a g, d a = sum (x > 0 ? 0 : x g), the sum in a fixed order
+ * in fp64 (bitwise reproducible like every other output).  A null widths or an
+ * activation other than 0 / 1 is NRK_EINVAL, any other shape outside the above
+ * NRK_EUNSUPPORTED, both before a pointer is touched. */
+size_t nrk_din_train_mlp_workspace_bytes(int64_t n_table_rows, int dim, int table_dtype, int n_user, int n_item,
+                                         int n_ctx, int n_layers, const int32_t* widths, int activation,
+                                         int64_t batch, int seq_len);
+int64_t nrk_din_train_mlp_n_weights(int dim, int n_user, int n_item, int n_ctx, int n_layers, const int32_t* widths,
+                                    int activation);
+int nrk_din_train_grad_mlp(const float* table, int64_t n_table_rows, int dim, int table_dtype, const int64_t* row_base,
+                           int n_user, int n_item, int n_ctx, const float* weights, int n_layers,
+                           const int32_t* widths, int activation, const int32_t* user_idx, const int32_t* item_idx,
+                           const int32_t* hist_idx, const int32_t* ctx_idx, const float* mask, const float* labels,
+                           int64_t batch, int seq_len, float* loss, float* w_grad, int32_t* t_rows, float* t_vals,
+                           int32_t* t_count, void* workspace, size_t workspace_bytes, nrk_stream_t stream);
+
 /* One torch.optim.Adam step with dense semantics over the packed weights
  * and the whole table (as nrk_tt_adam_step): rows absent from the list have
  * g = 0 and still move; a row with m = v = g = 0 is left untouched. */

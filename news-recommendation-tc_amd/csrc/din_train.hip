@@ -15,8 +15,11 @@
 //             dt_colstat      mean and unbiased std of every (t,h) column
 //             dt_att_out      Dice, Linear(36 -> 1), mask, sum_t w k, and the
 //                             MLP input row [user | ctx | candidate | history]
-//             dt_gemm / dt_colstat / dt_dice_fwd, twice; dt_head (loss)
-//   backward  dt_dice_sums + dt_dice_bwd per MLP Dice, dt_gemm for dW / dA
+//             per hidden layer dt_gemm, then dt_colstat / dt_dice_fwd (Dice)
+//             or dt_prelu_fwd (PReLU); the last layer's activation is
+//             dt_head's (loss)
+//   backward  per hidden layer, last first: dt_dice_sums + dt_dice_bwd (Dice)
+//             or dt_prelu_bwd + dt_slope_final (PReLU), dt_gemm for dW / dA
 //             dt_att_ds       d score[b,t]
 //             dt_dice_sums    the two column sums of the attention Dice
 //             dt_att_bwd      d z (in place), d k, d q, and per block the
@@ -40,6 +43,12 @@
 // gradient is NaN there; the std term is dropped here), and |logit| so large
 // that p (1 - p) underflows in BCELoss (|x| >~ 15).  Loss and gradients stay
 // finite in both cases; parity with torch is not claimed.
+//
+// The final MLP has 1 to 4 hidden layers, all Dice or all nn.PReLU() (one
+// trained slope per layer, torch's convention at the kink: y = x > 0 ? x : a x,
+// dx = x > 0 ? g : a g, da = sum (x > 0 ? 0 : x g)).  A PReLU layer has no batch
+// statistics and launches none of the Dice passes; the attention unit is Dice
+// under either activation (DIN.py:188).
 //
 // The Adam sweep is train_common.h's, with one table.
 #include <algorithm>
@@ -287,30 +296,84 @@ __global__ __launch_bounds__(256) void dt_dice_bwd_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------ PReLU --
+// nn.PReLU() with its one slope, torch's convention at the kink (x = 0 takes
+// the slope's side in the forward and in both gradients).
+__device__ __forceinline__ float dt_prelu(float x, float a) { return x > 0.0f ? x : a * x; }
+
+__global__ __launch_bounds__(256) void dt_prelu_fwd_kernel(const float* __restrict__ x,
+                                                           const float* __restrict__ slope, int64_t n,
+                                                           float* __restrict__ y) {
+    const float a = slope[0];
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        y[i] = dt_prelu(x[i], a);
+}
+
+constexpr int DT_SLOPE_BLOCKS = 256;  // blocks of dt_prelu_bwd: the partials dt_slope_final adds in order
+
+// g [n] (d of the PReLU output) -> d of its input, in place, and the block's
+// part of d slope = sum (x > 0 ? 0 : x g): a thread's elements ascending in
+// fp64, the wave tree, the four waves in order.
+__global__ __launch_bounds__(256) void dt_prelu_bwd_kernel(const float* __restrict__ x,
+                                                           const float* __restrict__ slope, int64_t n,
+                                                           float* __restrict__ g, double* __restrict__ part) {
+    __shared__ double wp[4];
+    const float a = slope[0];
+    double s = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float xv = x[i], gv = g[i];
+        if (!(xv > 0.0f)) {
+            s += (double)xv * (double)gv;
+            g[i] = a * gv;
+        }
+    }
+    s = wave_sum_f64(s);
+    if ((threadIdx.x & 63) == 0) wp[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((wp[0] + wp[1]) + wp[2]) + wp[3];
+}
+
+// d slope: the block partials in block order, rounded once
+__global__ void dt_slope_final_kernel(const double* __restrict__ part, int nblk, float* __restrict__ g_slope) {
+    if (threadIdx.x || blockIdx.x) return;
+    double t = 0.0;
+    for (int k = 0; k < nblk; ++k) t += part[k];
+    g_slope[0] = (float)t;
+}
+
 // ------------------------------------------------------------------- head --
-// One wave per sample: a2 = dice(z2), logit = w2 . a2 + b2, p = sigmoid,
-// BCELoss (log clamped at -100) and its gradient as torch forms it:
-// (p - y) / max((1 - p) p, 1e-12) / B, then sigmoid's (1 - p) p.
-// hb[b] = [g a2 | g] (column sums: d w2, d b2), da2[b] = g w2.
-__global__ __launch_bounds__(256) void dt_head_kernel(const float* __restrict__ z2, const double* __restrict__ mu,
-                                                      const double* __restrict__ sd, const float* __restrict__ w2,
-                                                      const float* __restrict__ b2, const float* __restrict__ label,
-                                                      int B, int H2, float* __restrict__ loss_b,
-                                                      float* __restrict__ hb, float* __restrict__ da2) {
+// One wave per sample over the last hidden layer: a = act(z) (ACT: Dice with
+// the column statistics, or PReLU with the layer's slope), logit = w . a + b,
+// p = sigmoid, BCELoss (log clamped at -100) and its gradient as torch forms
+// it: (p - y) / max((1 - p) p, 1e-12) / B, then sigmoid's (1 - p) p.
+// hb[b] = [g a | g] (column sums: d w, d b), da[b] = g w.
+template <int ACT>
+__global__ __launch_bounds__(256) void dt_head_kernel(const float* __restrict__ z, const double* __restrict__ mu,
+                                                      const double* __restrict__ sd, const float* __restrict__ slope,
+                                                      const float* __restrict__ w, const float* __restrict__ bo,
+                                                      const float* __restrict__ label, int B, int H,
+                                                      float* __restrict__ loss_b, float* __restrict__ hb,
+                                                      float* __restrict__ da) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
+    const float sl = ACT == DIN_ACT_PRELU ? slope[0] : 0.0f;
+    auto act = [&](int c) {
+        const float x = z[(int64_t)b * H + c];
+        if constexpr (ACT == DIN_ACT_PRELU) return dt_prelu(x, sl);
+        else return dt_dice(x, mu[c], sd[c]);
+    };
     double s = 0.0;
-    for (int c = lane; c < H2; c += WAVE) s += (double)w2[c] * (double)dt_dice(z2[(int64_t)b * H2 + c], mu[c], sd[c]);
-    const float logit = (float)(wave_sum_f64(s) + (double)b2[0]);
+    for (int c = lane; c < H; c += WAVE) s += (double)w[c] * (double)act(c);
+    const float logit = (float)(wave_sum_f64(s) + (double)bo[0]);
     const float p = 1.0f / (1.0f + expf(-logit)), y = label[b];
     if (lane == 0) loss_b[b] = -(y * fmaxf(logf(p), -100.0f) + (1.0f - y) * fmaxf(log1pf(-p), -100.0f));
     const float gi = (1.0f / (float)B) * (p - y) / fmaxf((1.0f - p) * p, 1e-12f);
     const float g = gi * (1.0f - p) * p;
-    for (int c = lane; c < H2; c += WAVE) {
-        hb[(int64_t)b * (H2 + 1) + c] = g * dt_dice(z2[(int64_t)b * H2 + c], mu[c], sd[c]);
-        da2[(int64_t)b * H2 + c] = g * w2[c];
+    for (int c = lane; c < H; c += WAVE) {
+        hb[(int64_t)b * (H + 1) + c] = g * act(c);
+        da[(int64_t)b * H + c] = g * w[c];
     }
-    if (lane == 0) hb[(int64_t)b * (H2 + 1) + H2] = g;
+    if (lane == 0) hb[(int64_t)b * (H + 1) + H] = g;
 }
 
 // mean of the per-sample losses: 16 slices, fixed tree (as tt_wgrad_kernel)
@@ -693,15 +756,18 @@ __global__ __launch_bounds__(256) void dt_emb_long_kernel(const int32_t* __restr
 }
 
 // ------------------------------------------------------------------- host --
+// L hidden layers of widths H[0 .. L), layer n reading K(n) inputs; act: DIN_ACT_*
 struct DtShape {
-    int Fu, NI, Fc, H1, H2, B, T, Di, IN, S;
+    int Fu, NI, Fc, L, H[DIN_MAX_LAYERS], act, B, T, Di, IN, S;
     int64_t R, N;
+    int K(int n) const { return n ? H[n - 1] : IN; }
 };
 
 // packed weights: att_w0 [36, 4 Di] | att_b0 [36] | att_w1 [36] | att_b1 [1] |
-// mlp_w0 [H1, IN] | mlp_b0 [H1] | mlp_w1 [H2, H1] | mlp_b1 [H2] | mlp_w2 [H2] | mlp_b2 [1]
+// per hidden layer n: w[n] [H[n], K(n)] | b[n] [H[n]] | (PReLU: slope[n] [1]) |
+// then w_out [H[L - 1]] | b_out [1]
 struct DtOff {
-    int64_t aw0, ab0, aw1, ab1, w0, b0, w1, b1, w2, b2, n;
+    int64_t aw0, ab0, aw1, ab1, w[DIN_MAX_LAYERS], b[DIN_MAX_LAYERS], slope[DIN_MAX_LAYERS], w_out, b_out, n;
 };
 static DtOff dt_offsets(const DtShape& s) {
     DtOff o{};
@@ -715,31 +781,40 @@ static DtOff dt_offsets(const DtShape& s) {
     o.ab0 = take(36);
     o.aw1 = take(36);
     o.ab1 = take(1);
-    o.w0 = take((int64_t)s.H1 * s.IN);
-    o.b0 = take(s.H1);
-    o.w1 = take((int64_t)s.H2 * s.H1);
-    o.b1 = take(s.H2);
-    o.w2 = take(s.H2);
-    o.b2 = take(1);
+    for (int n = 0; n < s.L; ++n) {
+        o.w[n] = take((int64_t)s.H[n] * s.K(n));
+        o.b[n] = take(s.H[n]);
+        if (s.act == DIN_ACT_PRELU) o.slope[n] = take(1);
+    }
+    o.w_out = take(s.H[s.L - 1]);
+    o.b_out = take(1);
     o.n = p;
     return o;
 }
 
+// `dice_only`: nrk_din_train_grad's own refusal of any activation but Dice
 static int dt_check(const char* fn, int64_t n_rows, int dim, int table_dtype, int n_user, int n_item, int n_ctx,
-                    int h1, int h2, int activation, int64_t batch, int seq_len, DtShape* s) {
+                    int n_layers, const int32_t* widths, int activation, bool dice_only, int64_t batch, int seq_len,
+                    DtShape* s) {
     auto fail = [&](int rc, const char* msg) {
         set_error(std::string(fn) + ": " + msg);
         return rc;
     };
     if (dim != DIN_E) return fail(NRK_EUNSUPPORTED, "training is built for din_embedding_dim == 32");
     if (table_dtype != 0) return fail(NRK_EUNSUPPORTED, "training needs fp32 tables");
-    if (activation != 0) return fail(NRK_EUNSUPPORTED, "training implements the Dice activation only");
+    if (dice_only && activation != 0) return fail(NRK_EUNSUPPORTED, "training implements the Dice activation only");
+    if (activation != DIN_ACT_DICE && activation != DIN_ACT_PRELU)
+        return fail(NRK_EINVAL, "activation must be 0 (dice) or 1 (prelu)");
     if (!(n_item == 1 || n_item == 2 || n_item == 4 || n_item == 8))
         return fail(NRK_EUNSUPPORTED, "n_item must be 1, 2, 4 or 8");
     if (n_user < 1 || n_user > DT_MAXF || n_ctx < 0 || n_ctx > DT_MAXF)
         return fail(NRK_EUNSUPPORTED, "n_user must be in [1, 64] and n_ctx in [0, 64]");
-    if (h1 < 1 || h1 > DT_MAXH || h2 < 1 || h2 > DT_MAXH)
-        return fail(NRK_EUNSUPPORTED, "MLP hidden widths must be in [1, 1024]");
+    if (n_layers < 1 || n_layers > DIN_MAX_LAYERS) return fail(NRK_EUNSUPPORTED, "n_layers must be in [1, 4]");
+    if (!widths) return fail(NRK_EINVAL, "null pointer (widths)");
+    for (int n = 0; n < n_layers; ++n)
+        if (widths[n] < 1 || widths[n] > DT_MAXH)
+            return fail(NRK_EUNSUPPORTED, dice_only ? "MLP hidden widths must be in [1, 1024]"
+                                                    : "hidden widths must be in [1, 1024]");
     if (batch < 2 || batch > DT_MAXB)
         return fail(NRK_EUNSUPPORTED, "batch must be in [2, 8192] (Dice uses the batch std)");
     if (seq_len < 1 || seq_len > DT_MAXT) return fail(NRK_EUNSUPPORTED, "seq_len must be in [1, 128]");
@@ -747,8 +822,9 @@ static int dt_check(const char* fn, int64_t n_rows, int dim, int table_dtype, in
     s->Fu = n_user;
     s->NI = n_item;
     s->Fc = n_ctx;
-    s->H1 = h1;
-    s->H2 = h2;
+    s->L = n_layers;
+    for (int n = 0; n < n_layers; ++n) s->H[n] = widths[n];
+    s->act = activation;
     s->B = (int)batch;
     s->T = seq_len;
     s->Di = n_item * 32;
@@ -760,9 +836,12 @@ static int dt_check(const char* fn, int64_t n_rows, int dim, int table_dtype, in
 }
 
 struct DtWs {
-    float *z, *wbuf, *ds, *dsT, *Abuf, *Gq, *x0, *dx0, *z1, *a1, *da1, *z2, *da2, *hb, *loss_b, *dk;
-    double *gpart, *gemm_part, *epart;  // partial sums that a later kernel adds in order
-    double *mu_a, *sd_a, *S_a, *mu1, *sd1, *S1, *mu2, *sd2, *S2;  // Dice statistics and backward sums
+    float *z, *wbuf, *ds, *dsT, *Abuf, *Gq, *x0, *dx0, *hb, *loss_b, *dk;
+    // per hidden layer: pre-activation, activation (not the last layer's: the head forms it), d activation
+    float *zn[DIN_MAX_LAYERS], *an[DIN_MAX_LAYERS], *dan[DIN_MAX_LAYERS];
+    double *gpart, *gemm_part, *epart, *spart;  // partial sums that a later kernel adds in order
+    double *mu_a, *sd_a, *S_a;                  // Dice statistics and backward sums: the attention's,
+    double *mu[DIN_MAX_LAYERS], *sd[DIN_MAX_LAYERS], *Sn[DIN_MAX_LAYERS];  // and a Dice layer's
     uint32_t *keys, *keys2;
     int32_t *cid, *cid2, *flag, *seg, *starts;
     void* sort_tmp;
@@ -798,20 +877,24 @@ static DtWs dt_layout(void* base, const DtShape& s) {
     w.gpart = (double*)a.take(8 * (size_t)w.nblk * 2 * 36 * s.Di);
     w.x0 = (float*)a.take(f * B * s.IN);
     w.dx0 = (float*)a.take(f * B * s.IN);
-    w.z1 = (float*)a.take(f * B * s.H1);
-    w.mu1 = (double*)a.take(8 * (size_t)s.H1);
-    w.sd1 = (double*)a.take(8 * (size_t)s.H1);
-    w.a1 = (float*)a.take(f * B * s.H1);
-    w.da1 = (float*)a.take(f * B * s.H1);
-    w.S1 = (double*)a.take(8 * 3 * (size_t)s.H1);
-    w.z2 = (float*)a.take(f * B * s.H2);
-    w.mu2 = (double*)a.take(8 * (size_t)s.H2);
-    w.sd2 = (double*)a.take(8 * (size_t)s.H2);
-    w.da2 = (float*)a.take(f * B * s.H2);
-    w.S2 = (double*)a.take(8 * 3 * (size_t)s.H2);
-    w.hb = (float*)a.take(f * B * (s.H2 + 1));
+    int maxH = 36, maxK = s.IN;  // gemm_part holds the split-K slices of the largest dW (and of Gq [36, Di])
+    for (int n = 0; n < s.L; ++n) {
+        const size_t H = s.H[n];
+        maxH = std::max(maxH, s.H[n]);
+        maxK = std::max(maxK, s.K(n));
+        w.zn[n] = (float*)a.take(f * B * H);
+        if (s.act == DIN_ACT_DICE) {
+            w.mu[n] = (double*)a.take(8 * H);
+            w.sd[n] = (double*)a.take(8 * H);
+        }
+        if (n < s.L - 1) w.an[n] = (float*)a.take(f * B * H);
+        w.dan[n] = (float*)a.take(f * B * H);
+        if (s.act == DIN_ACT_DICE) w.Sn[n] = (double*)a.take(8 * 3 * H);
+    }
+    if (s.act == DIN_ACT_PRELU) w.spart = (double*)a.take(8 * DT_SLOPE_BLOCKS);
+    w.hb = (float*)a.take(f * B * (s.H[s.L - 1] + 1));
     w.loss_b = (float*)a.take(f * B);
-    w.gemm_part = (double*)a.take(8 * (size_t)w.ksplit * std::max({s.H1, s.H2, 36}) * std::max(s.IN, s.H1));
+    w.gemm_part = (double*)a.take(8 * (size_t)w.ksplit * maxH * maxK);
     w.dk = (float*)a.take(f * B * s.T * s.Di);
     w.epart = (double*)a.take(8 * 2 * 32 * (size_t)((s.N + DT_PIECE - 1) / DT_PIECE));
     w.keys = (uint32_t*)a.take(4 * (size_t)s.N);
@@ -842,7 +925,8 @@ template <int NI>
 static int dt_run(const DtShape& s, const DtWs& w, const DtIdx& ix, const float* wts, const float* labels, float* loss,
                   float* wg, int32_t* rows, float* vals, int32_t* count, hipStream_t st) {
     const DtOff o = dt_offsets(s);
-    const int B = s.B, T = s.T, Di = s.Di, IN = s.IN, H1 = s.H1, H2 = s.H2, C = T * 36, WS = Di + 1;
+    const int B = s.B, T = s.T, Di = s.Di, IN = s.IN, L = s.L, C = T * 36, WS = Di + 1;
+    const bool dice = s.act == DIN_ACT_DICE;
     auto eg = [](int64_t n) { return grid_for(n, 256, 2048); };  // the grid-stride elementwise kernels
     // ---- forward
     const size_t lds_fwd = sizeof(float) * (36 * WS + Di + 36) + sizeof(int) * T * NI;
@@ -851,29 +935,54 @@ static int dt_run(const DtShape& s, const DtWs& w, const DtIdx& ix, const float*
     const size_t lds_out = sizeof(float) * (T * 36 + T + Di) + sizeof(int) * T * NI;
     dt_att_out_kernel<NI><<<B, 256, lds_out, st>>>(ix, w.z, w.mu_a, w.sd_a, wts + o.aw1, wts + o.ab1, IN, w.wbuf, w.x0);
     NRK_CHECK_LAUNCH();
-    if (dt_gemm(st, w.x0, IN, 1, wts + o.w0, 1, IN, wts + o.b0, w.z1, H1, B, H1, IN, 1, nullptr)) return NRK_EHIP;
-    dt_colstat_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.z1, B, H1, w.mu1, w.sd1);
-    dt_dice_fwd_kernel<<<eg((int64_t)B * H1), 256, 0, st>>>(w.z1, w.mu1, w.sd1, (int64_t)B * H1, H1, w.a1);
-    if (dt_gemm(st, w.a1, H1, 1, wts + o.w1, 1, H1, wts + o.b1, w.z2, H2, B, H2, H1, 1, nullptr)) return NRK_EHIP;
-    dt_colstat_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.z2, B, H2, w.mu2, w.sd2);
-    dt_head_kernel<<<(B + 3) / 4, 256, 0, st>>>(w.z2, w.mu2, w.sd2, wts + o.w2, wts + o.b2, labels, B, H2, w.loss_b,
-                                                w.hb, w.da2);
-    dt_loss_kernel<<<1, 1024, 0, st>>>(w.loss_b, B, loss);
-    NRK_CHECK_LAUNCH();
-    // ---- backward: MLP
-    dt_colsum_kernel<<<(H2 + 1 + 15) / 16, 1024, 0, st>>>(w.hb, B, H2 + 1, wg + o.w2);  // d w2 | d b2
-    dt_dice_sums_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.z2, w.mu2, w.sd2, w.da2, H2, 1, nullptr, B, H2, w.S2);
-    dt_dice_bwd_kernel<<<eg((int64_t)B * H2), 256, 0, st>>>(w.z2, w.mu2, w.sd2, w.S2, B, H2, w.da2);  // da2 := dz2
-    dt_colsum_kernel<<<(H2 + 15) / 16, 1024, 0, st>>>(w.da2, B, H2, wg + o.b1);
-    if (dt_gemm(st, w.da2, 1, H2, w.a1, H1, 1, nullptr, wg + o.w1, H1, H2, H1, B, w.ksplit, w.gemm_part))
-        return NRK_EHIP;
-    if (dt_gemm(st, w.da2, H2, 1, wts + o.w1, H1, 1, nullptr, w.da1, H1, B, H1, H2, 1, nullptr)) return NRK_EHIP;
-    dt_dice_sums_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.z1, w.mu1, w.sd1, w.da1, H1, 1, nullptr, B, H1, w.S1);
-    dt_dice_bwd_kernel<<<eg((int64_t)B * H1), 256, 0, st>>>(w.z1, w.mu1, w.sd1, w.S1, B, H1, w.da1);  // da1 := dz1
-    dt_colsum_kernel<<<(H1 + 15) / 16, 1024, 0, st>>>(w.da1, B, H1, wg + o.b0);
-    if (dt_gemm(st, w.da1, 1, H1, w.x0, IN, 1, nullptr, wg + o.w0, IN, H1, IN, B, w.ksplit, w.gemm_part))
-        return NRK_EHIP;
-    if (dt_gemm(st, w.da1, H1, 1, wts + o.w0, IN, 1, nullptr, w.dx0, IN, B, IN, H1, 1, nullptr)) return NRK_EHIP;
+    // hidden layer n: z_n = a_{n-1} W_n^T + b_n (a_{-1} = x0), the Dice statistics of its columns,
+    // a_n = act(z_n); the last layer's activation belongs to the head
+    for (int n = 0; n < L; ++n) {
+        const int H = s.H[n], K = s.K(n);
+        const int64_t BH = (int64_t)B * H;
+        const float* in = n ? w.an[n - 1] : w.x0;
+        if (dt_gemm(st, in, K, 1, wts + o.w[n], 1, K, wts + o.b[n], w.zn[n], H, B, H, K, 1, nullptr)) return NRK_EHIP;
+        if (dice) dt_colstat_kernel<<<(H + 15) / 16, 1024, 0, st>>>(w.zn[n], B, H, w.mu[n], w.sd[n]);
+        if (n == L - 1) break;
+        if (dice) dt_dice_fwd_kernel<<<eg(BH), 256, 0, st>>>(w.zn[n], w.mu[n], w.sd[n], BH, H, w.an[n]);
+        else dt_prelu_fwd_kernel<<<eg(BH), 256, 0, st>>>(w.zn[n], wts + o.slope[n], BH, w.an[n]);
+    }
+    {
+        const int n = L - 1, H = s.H[n];
+        if (dice)
+            dt_head_kernel<DIN_ACT_DICE><<<(B + 3) / 4, 256, 0, st>>>(w.zn[n], w.mu[n], w.sd[n], nullptr, wts + o.w_out,
+                                                                      wts + o.b_out, labels, B, H, w.loss_b, w.hb,
+                                                                      w.dan[n]);
+        else
+            dt_head_kernel<DIN_ACT_PRELU><<<(B + 3) / 4, 256, 0, st>>>(w.zn[n], nullptr, nullptr, wts + o.slope[n],
+                                                                       wts + o.w_out, wts + o.b_out, labels, B, H,
+                                                                       w.loss_b, w.hb, w.dan[n]);
+        dt_loss_kernel<<<1, 1024, 0, st>>>(w.loss_b, B, loss);
+        NRK_CHECK_LAUNCH();
+        // ---- backward: MLP
+        dt_colsum_kernel<<<(H + 1 + 15) / 16, 1024, 0, st>>>(w.hb, B, H + 1, wg + o.w_out);  // d w_out | d b_out
+    }
+    // dan[n] holds d a_n and becomes d z_n in place; then d b_n, d W_n and d a_{n-1} (d x0 for n = 0)
+    for (int n = L - 1; n >= 0; --n) {
+        const int H = s.H[n], K = s.K(n);
+        const int64_t BH = (int64_t)B * H;
+        float* dz = w.dan[n];
+        if (dice) {
+            dt_dice_sums_kernel<<<(H + 15) / 16, 1024, 0, st>>>(w.zn[n], w.mu[n], w.sd[n], dz, H, 1, nullptr, B, H,
+                                                                w.Sn[n]);
+            dt_dice_bwd_kernel<<<eg(BH), 256, 0, st>>>(w.zn[n], w.mu[n], w.sd[n], w.Sn[n], B, H, dz);
+        } else {
+            const unsigned nb = grid_for(BH, 256, DT_SLOPE_BLOCKS);
+            dt_prelu_bwd_kernel<<<nb, 256, 0, st>>>(w.zn[n], wts + o.slope[n], BH, dz, w.spart);
+            dt_slope_final_kernel<<<1, 64, 0, st>>>(w.spart, (int)nb, wg + o.slope[n]);
+        }
+        dt_colsum_kernel<<<(H + 15) / 16, 1024, 0, st>>>(dz, B, H, wg + o.b[n]);
+        if (dt_gemm(st, dz, 1, H, n ? w.an[n - 1] : w.x0, K, 1, nullptr, wg + o.w[n], K, H, K, B, w.ksplit,
+                    w.gemm_part))
+            return NRK_EHIP;
+        if (dt_gemm(st, dz, H, 1, wts + o.w[n], K, 1, nullptr, n ? w.dan[n - 1] : w.dx0, K, B, K, H, 1, nullptr))
+            return NRK_EHIP;
+    }
     NRK_CHECK_LAUNCH();
     // ---- backward: attention
     dt_att_ds_kernel<NI><<<B, 256, 0, st>>>(ix, w.dx0, IN, w.ds);
@@ -936,12 +1045,38 @@ using namespace nrk;
 
 extern "C" {
 
+// The one dispatch path of both entry points, after dt_check (ws_fn: the caller's workspace query).
+static int dt_grad(const char* fn, const char* ws_fn, const DtShape& s, const float* table, const int64_t* row_base,
+                   const float* weights, const int32_t* user_idx, const int32_t* item_idx, const int32_t* hist_idx,
+                   const int32_t* ctx_idx, const float* mask, const float* labels, float* loss, float* w_grad,
+                   int32_t* t_rows, float* t_vals, int32_t* t_count, void* workspace, size_t workspace_bytes,
+                   nrk_stream_t stream) {
+    auto fail = [&](const char* msg) {
+        set_error(std::string(fn) + ": " + msg);
+        return NRK_EINVAL;
+    };
+    if (!(table && row_base && weights && user_idx && item_idx && hist_idx && (ctx_idx || s.Fc == 0) && mask &&
+          labels && loss && w_grad && t_rows && t_vals && t_count && workspace))
+        return fail("null pointer");
+    const DtWs w = dt_layout(workspace, s);
+    if (workspace_bytes < w.bytes) return fail((std::string("workspace too small (") + ws_fn + ")").c_str());
+    const DtIdx ix{table, row_base, user_idx, item_idx, hist_idx, ctx_idx, mask, s.Fu, s.Fc, s.B, s.T};
+    hipStream_t st = as_stream(stream);
+    switch (s.NI) {
+        case 1: return dt_run<1>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        case 2: return dt_run<2>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        case 4: return dt_run<4>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+        default: return dt_run<8>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
+    }
+}
+
 size_t nrk_din_train_workspace_bytes(int64_t n_table_rows, int dim, int table_dtype, int n_user, int n_item,
                                      int n_ctx, int h1, int h2, int activation, int64_t batch, int seq_len) {
     clear_error();
     DtShape s{};
-    if (dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, h1, h2, activation, batch, seq_len,
-                 &s) != NRK_OK)
+    const int32_t widths[2] = {h1, h2};
+    if (dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, 2, widths, activation, true, batch,
+                 seq_len, &s) != NRK_OK)
         return 0;
     return dt_layout(nullptr, s).bytes;
 }
@@ -954,22 +1089,49 @@ int nrk_din_train_grad(const float* table, int64_t n_table_rows, int dim, int ta
                        size_t workspace_bytes, nrk_stream_t stream) {
     clear_error();
     DtShape s{};
-    const int rc = dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, h1, h2, activation, batch,
-                            seq_len, &s);
+    const int32_t widths[2] = {h1, h2};
+    const int rc = dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, 2, widths, activation,
+                            true, batch, seq_len, &s);
     if (rc != NRK_OK) return rc;
-    NRK_REQUIRE(table && row_base && weights && user_idx && item_idx && hist_idx && (ctx_idx || n_ctx == 0) && mask &&
-                    labels && loss && w_grad && t_rows && t_vals && t_count && workspace,
-                "null pointer");
-    const DtWs w = dt_layout(workspace, s);
-    NRK_REQUIRE(workspace_bytes >= w.bytes, "workspace too small (nrk_din_train_workspace_bytes)");
-    const DtIdx ix{table, row_base, user_idx, item_idx, hist_idx, ctx_idx, mask, n_user, n_ctx, s.B, s.T};
-    hipStream_t st = as_stream(stream);
-    switch (n_item) {
-        case 1: return dt_run<1>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
-        case 2: return dt_run<2>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
-        case 4: return dt_run<4>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
-        default: return dt_run<8>(s, w, ix, weights, labels, loss, w_grad, t_rows, t_vals, t_count, st);
-    }
+    return dt_grad(__func__, "nrk_din_train_workspace_bytes", s, table, row_base, weights, user_idx, item_idx,
+                   hist_idx, ctx_idx, mask, labels, loss, w_grad, t_rows, t_vals, t_count, workspace, workspace_bytes,
+                   stream);
+}
+
+size_t nrk_din_train_mlp_workspace_bytes(int64_t n_table_rows, int dim, int table_dtype, int n_user, int n_item,
+                                         int n_ctx, int n_layers, const int32_t* widths, int activation,
+                                         int64_t batch, int seq_len) {
+    clear_error();
+    DtShape s{};
+    if (dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, n_layers, widths, activation, false,
+                 batch, seq_len, &s) != NRK_OK)
+        return 0;
+    return dt_layout(nullptr, s).bytes;
+}
+
+int64_t nrk_din_train_mlp_n_weights(int dim, int n_user, int n_item, int n_ctx, int n_layers, const int32_t* widths,
+                                    int activation) {
+    clear_error();
+    DtShape s{};
+    if (dt_check(__func__, 1, dim, 0, n_user, n_item, n_ctx, n_layers, widths, activation, false, 2, 1, &s) != NRK_OK)
+        return 0;
+    return dt_offsets(s).n;
+}
+
+int nrk_din_train_grad_mlp(const float* table, int64_t n_table_rows, int dim, int table_dtype, const int64_t* row_base,
+                           int n_user, int n_item, int n_ctx, const float* weights, int n_layers,
+                           const int32_t* widths, int activation, const int32_t* user_idx, const int32_t* item_idx,
+                           const int32_t* hist_idx, const int32_t* ctx_idx, const float* mask, const float* labels,
+                           int64_t batch, int seq_len, float* loss, float* w_grad, int32_t* t_rows, float* t_vals,
+                           int32_t* t_count, void* workspace, size_t workspace_bytes, nrk_stream_t stream) {
+    clear_error();
+    DtShape s{};
+    const int rc = dt_check(__func__, n_table_rows, dim, table_dtype, n_user, n_item, n_ctx, n_layers, widths,
+                            activation, false, batch, seq_len, &s);
+    if (rc != NRK_OK) return rc;
+    return dt_grad(__func__, "nrk_din_train_mlp_workspace_bytes", s, table, row_base, weights, user_idx, item_idx,
+                   hist_idx, ctx_idx, mask, labels, loss, w_grad, t_rows, t_vals, t_count, workspace, workspace_bytes,
+                   stream);
 }
 
 int nrk_din_adam_step(float* weights, float* w_m, float* w_v, const float* w_grad, int64_t n_weights, float* table,

@@ -118,6 +118,10 @@ SIGNATURES = {
     "nrk_din_train_workspace_bytes": (SZ, [I64, INT, INT, INT, INT, INT, INT, INT, INT, I64, INT]),
     "nrk_din_train_grad": (INT, [P, I64, INT, INT, P, INT, INT, INT, P, INT, INT, INT, P, P, P, P, P, P, I64, INT,
                                  P, P, P, P, P, P, SZ, P]),
+    "nrk_din_train_mlp_workspace_bytes": (SZ, [I64, INT, INT, INT, INT, INT, INT, P, INT, I64, INT]),
+    "nrk_din_train_mlp_n_weights": (I64, [INT, INT, INT, INT, INT, P, INT]),
+    "nrk_din_train_grad_mlp": (INT, [P, I64, INT, INT, P, INT, INT, INT, P, INT, P, INT, P, P, P, P, P, P, I64, INT,
+                                     P, P, P, P, P, P, SZ, P]),
     "nrk_din_adam_step": (INT, [P, P, P, P, I64, P, P, P, I64, INT, P, P, P, F64, F64, F64, F64, I64, P]),
 }
 

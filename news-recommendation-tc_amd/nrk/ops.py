@@ -936,23 +936,36 @@ def din_workspace(p: DinParams, B, T, device, batch_size=None):
 DIN_GROUPS = ("user_profile_embedding_dict", "item_embedding_dict", "context_embedding_dict")
 
 
-def din_state_keys(user_feats, item_feats, ctx_feats):
+def din_state_keys(user_feats, item_feats, ctx_feats, hidden=(200, 80), activation="dice"):
     """(table keys, packed-weight keys, alpha keys, DINModel.state_dict() key
-    order) of a two-hidden-layer Dice DINModel (DIN.py:133-212)."""
+    order) of a DINModel (DIN.py:133-212) with ``len(hidden)`` MLP hidden
+    layers.  The packed-weight keys are in the order of the packed vector;
+    under "prelu" they hold each layer's slope ``mlp.{2n+1}.weight`` after its
+    bias, and only the attention's Dice has an alpha."""
+    L = len(hidden)
     tabs = [f"{g}.{f}.weight" for g, fs in zip(DIN_GROUPS, (user_feats, item_feats, ctx_feats)) for f in fs]
     wts = ["activation_unit.mlp.0.weight", "activation_unit.mlp.0.bias", "activation_unit.mlp.2.weight",
-           "activation_unit.mlp.2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias",
-           "mlp.4.weight", "mlp.4.bias"]
-    alphas = ["activation_unit.mlp.1.alpha", "mlp.1.alpha", "mlp.3.alpha"]
-    order = tabs + wts[:2] + alphas[:1] + wts[2:6] + alphas[1:2] + wts[6:8] + alphas[2:] + wts[8:]
-    return tabs, wts, alphas, order
+           "activation_unit.mlp.2.bias"]
+    alphas = ["activation_unit.mlp.1.alpha"]
+    order = tabs + wts[:2] + alphas + wts[2:]
+    for n in range(L):
+        act = f"mlp.{2 * n + 1}.weight" if activation == "prelu" else f"mlp.{2 * n + 1}.alpha"
+        layer = [f"mlp.{2 * n}.weight", f"mlp.{2 * n}.bias"]
+        wts += layer + ([act] if activation == "prelu" else [])
+        alphas += [] if activation == "prelu" else [act]
+        order += layer + [act]
+    wts += [f"mlp.{2 * L}.weight", f"mlp.{2 * L}.bias"]
+    return tabs, wts, alphas, order + wts[-2:]
 
 
 class DinTrainParams:
     """A DINModel's parameters with their Adam moments on the device in the
-    layout of nrk_din_train_grad: the per-feature embedding tables
-    concatenated row-wise (``row_base`` as DinParams), the Linear layers as one
-    packed vector, the Dice alphas (no gradient, never updated) as given.
+    layout of nrk_din_train_grad_mlp: the per-feature embedding tables
+    concatenated row-wise (``row_base`` as DinParams), the Linear layers and
+    the PReLU slopes as one packed vector, the Dice alphas (no gradient, never
+    updated) as given.  Depth (1 to 4 hidden layers), ``widths`` and
+    ``activation`` ("dice" or "prelu") are read off the state_dict's keys as
+    DinParams reads them; ``h1`` / ``h2`` name the widths of a two-layer model.
     Shapes outside the compiled training variants (din_embedding_dim != 32,
     item-feature counts other than 1, 2, 4, 8, bf16 tables, ...) raise
     NotImplementedError: they stay inference-only."""
@@ -966,7 +979,25 @@ class DinTrainParams:
             return np.ascontiguousarray(v, dtype=np.float32)
 
         self.feats = (list(user_feats), list(item_feats), list(ctx_feats))
-        self.tab_keys, self.w_keys, self.alpha_keys, self.order = din_state_keys(*self.feats)
+        # depth and activation off the keys (DIN.py:196-212): Linear mlp.{2n}, its activation at
+        # mlp.{2n+1} (Dice: ``alpha``; nn.PReLU(): ``weight`` (1,)), then the one-row Linear mlp.{2L}
+        L = 0
+        while f"mlp.{2 * L}.weight" in state_dict:
+            L += 1
+        L -= 1
+        if L < 1 or L > DIN_MAX_LAYERS:
+            raise NotImplementedError(f"the DIN kernels implement 1 to {DIN_MAX_LAYERS} MLP hidden layers, "
+                                      f"the state_dict has {L}")
+        kinds = {"prelu" if f"mlp.{2 * n + 1}.weight" in state_dict else "dice" for n in range(L)}
+        if any(f"mlp.{2 * n + 1}.weight" in state_dict and f"mlp.{2 * n + 1}.alpha" in state_dict
+               for n in range(L)) or len(kinds) != 1:
+            raise NotImplementedError("the MLP's activations mix Dice (alpha) and PReLU (weight) layers")
+        self.activation = kinds.pop()
+        self.widths = [int(np.shape(state_dict[f"mlp.{2 * n}.weight"])[0]) for n in range(L)]
+        if min(self.widths) < 1 or max(self.widths) > 1024:
+            raise NotImplementedError("the DIN kernels implement MLP widths of 1 to 1024")
+        self.tab_keys, self.w_keys, self.alpha_keys, self.order = din_state_keys(*self.feats, self.widths,
+                                                                                 self.activation)
         if table_dtype not in ("fp32", "bf16"):
             raise ValueError("table_dtype must be 'fp32' or 'bf16'")
         self.table_code = 0 if table_dtype == "fp32" else 1
@@ -981,13 +1012,27 @@ class DinTrainParams:
         self.n_rows = sum(self.vocab)
         ws = [arr(k) for k in self.w_keys]
         self.w_shapes = [w.shape for w in ws]
-        self.h1, self.h2 = int(ws[4].shape[0]), int(ws[6].shape[0])
+        self.h1 = self.widths[0]
+        if L == 2:
+            self.h2 = self.widths[1]
+        self._c_widths = (ctypes.c_int32 * L)(*self.widths)
         self.workspace_bytes(2, 1)  # refuses what the kernels are not built for
-        n_in = self.dim * (self.n_user + self.n_ctx + 2 * self.n_item)
-        exp = [(36, 4 * self.n_item * self.dim), (36,), (1, 36), (1,), (self.h1, n_in), (self.h1,),
-               (self.h2, self.h1), (self.h2,), (1, self.h2), (1,)]
+        cur = self.dim * (self.n_user + self.n_ctx + 2 * self.n_item)
+        exp = [(36, 4 * self.n_item * self.dim), (36,), (1, 36), (1,)]
+        for unit in self.widths:
+            exp += [(unit, cur), (unit,)] + ([(1,)] if self.activation == "prelu" else [])
+            cur = unit
+        exp += [(1, cur), (1,)]
+        if self.activation == "prelu" and any(np.shape(state_dict[f"mlp.{2 * n + 1}.weight"]) != (1,)
+                                              for n in range(L)):
+            raise NotImplementedError("nn.PReLU() with one slope per layer only (mlp.{2n+1}.weight of shape (1,))")
         if [tuple(s) for s in self.w_shapes] != exp:
             raise ValueError("state_dict shapes do not match the feature lists")
+        n_w = _lib.lib().nrk_din_train_mlp_n_weights(self.dim, self.n_user, self.n_item, self.n_ctx, L,
+                                                     ctypes.cast(self._c_widths, _P),
+                                                     DIN_ACTIVATIONS.index(self.activation))
+        if n_w != sum(int(np.prod(s)) for s in exp):
+            raise RuntimeError("nrk_din_train_mlp_n_weights disagrees with the packed layout")
         self.device = torch.device(device)
         self.table = torch.from_numpy(np.concatenate(tabs, 0)).to(self.device).contiguous()
         self.row_base = torch.from_numpy(np.cumsum([0] + self.vocab[:-1]).astype(np.int64)).to(self.device)
@@ -1001,10 +1046,12 @@ class DinTrainParams:
 
     def workspace_bytes(self, batch, seq_len):
         L = _lib.lib()
-        nb = L.nrk_din_train_workspace_bytes(self.n_rows, self.dim, self.table_code, self.n_user, self.n_item,
-                                             self.n_ctx, self.h1, self.h2, 0, batch, seq_len)
+        nb = L.nrk_din_train_mlp_workspace_bytes(self.n_rows, self.dim, self.table_code, self.n_user, self.n_item,
+                                                 self.n_ctx, len(self.widths), ctypes.cast(self._c_widths, _P),
+                                                 DIN_ACTIVATIONS.index(self.activation), batch, seq_len)
         if not nb:
-            raise NotImplementedError("nrk_din_train_workspace_bytes: " + L.nrk_last_error().decode(errors="replace"))
+            raise NotImplementedError("nrk_din_train_mlp_workspace_bytes: "
+                                      + L.nrk_last_error().decode(errors="replace"))
         return nb
 
     def split_weights(self, packed):
@@ -1095,8 +1142,10 @@ def din_train_grad(p: DinTrainParams, user, item, hist, ctx, mask, labels, out=N
         out = DinGrads(p, B, T)
     elif (out.batch, out.seq_len) != (B, T):
         raise ValueError("out: a DinGrads of another shape")
-    _lib.call("nrk_din_train_grad", _ptr(p.table), p.n_rows, p.dim, p.table_code, _ptr(p.row_base), p.n_user,
-              p.n_item, p.n_ctx, _ptr(p.weights), p.h1, p.h2, 0, _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx),
+    # two Dice layers run exactly what nrk_din_train_grad runs: one dispatch path behind both entries
+    _lib.call("nrk_din_train_grad_mlp", _ptr(p.table), p.n_rows, p.dim, p.table_code, _ptr(p.row_base), p.n_user,
+              p.n_item, p.n_ctx, _ptr(p.weights), len(p.widths), ctypes.cast(p._c_widths, _P),
+              DIN_ACTIVATIONS.index(p.activation), _ptr(user), _ptr(item), _ptr(hist), _ptr(ctx),
               _ptr(mask), _ptr(labels), B, T, _ptr(out.loss if loss is None else loss), _ptr(out.w_grad),
               _ptr(out.t_rows), _ptr(out.t_vals), _ptr(out.t_count), _ptr(ws), ws.numel(), _stream())
     return out

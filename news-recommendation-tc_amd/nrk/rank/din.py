@@ -248,6 +248,16 @@ class DINRanker(BaseRanker):
         return uv, iv, cv
 
     # ----------------------------------------------------------- model --
+    @staticmethod
+    def _check_model_config(activation, hidden):
+        """The model family the kernels serve and train."""
+        if activation not in ops.DIN_ACTIVATIONS:
+            raise NotImplementedError(f"the DIN kernels implement din_activation 'dice' and 'prelu', "
+                                      f"got {activation!r}")
+        if not 1 <= len(hidden) <= ops.DIN_MAX_LAYERS or not all(1 <= int(u) <= 1024 for u in hidden):
+            raise NotImplementedError(f"the DIN kernels implement 1 to {ops.DIN_MAX_LAYERS} MLP hidden layers of "
+                                      f"width 1 to 1024, got din_mlp_hidden_units = {hidden}")
+
     def load_model(self, load_dir=None):
         """DIN.py:1328-1399 (``load_dir``: a directory, default
         ``config.save_path``), or a DINModel state_dict (alternate entry)."""
@@ -267,13 +277,8 @@ class DINRanker(BaseRanker):
         self.label_encoders = load_pickle(encoders_path) if os.path.exists(encoders_path) else {}
         uv, iv, cv = self._prepare_vocab_dicts()
         activation = metadata.get("din_activation", "dice")
-        if activation not in ops.DIN_ACTIVATIONS:
-            raise NotImplementedError(f"the DIN kernels implement din_activation 'dice' and 'prelu', "
-                                      f"got {activation!r}")
         hidden = list(metadata.get("din_mlp_hidden_units", [200, 80]))
-        if not 1 <= len(hidden) <= ops.DIN_MAX_LAYERS or not all(1 <= int(u) <= 1024 for u in hidden):
-            raise NotImplementedError(f"the DIN kernels implement 1 to {ops.DIN_MAX_LAYERS} MLP hidden layers of "
-                                      f"width 1 to 1024, got din_mlp_hidden_units = {hidden}")
+        self._check_model_config(activation, hidden)
         model_path = os.path.join(load_dir, "din_model.pth")
         if not os.path.exists(model_path):
             raise FileNotFoundError(f"Model weights not found at: {model_path}")
@@ -317,10 +322,13 @@ class DINRanker(BaseRanker):
         nn.Embedding tables of the three groups, the ActivationUnit's two
         nn.Linear, the MLP's nn.Linear), so the generator is consumed exactly as
         ``DINModel(...)`` consumes it; a Dice ``alpha`` holds its layer's width,
-        as the reference's ``Dice(unit)`` leaves it (unused, never trained)."""
+        as the reference's ``Dice(unit)`` leaves it (unused, never trained).
+        Under ``din_activation="prelu"`` every hidden layer of the MLP holds an
+        ``nn.PReLU()`` slope instead: 0.25, drawn from no random numbers."""
         import torch.nn as nn
 
         dim, hidden = self.config.din_embedding_dim, list(self.config.din_mlp_hidden_units)
+        activation = self.config.din_activation
         torch.manual_seed(self.config.random_seed)
         sd = {}
         for grp, vocab in (("user_profile_embedding_dict", uv), ("item_embedding_dict", iv),
@@ -340,8 +348,11 @@ class DINRanker(BaseRanker):
         # Dice(unit) hands the layer width to ``alpha`` (DIN.py:72, :204): 36.0, then the MLP widths
         sd["activation_unit.mlp.1.alpha"] = torch.tensor(36.0, dtype=torch.float32)
         for n, unit in enumerate(hidden):
-            sd[f"mlp.{2 * n + 1}.alpha"] = torch.tensor(float(unit), dtype=torch.float32)
-        return {k: sd[k] for k in _expected_state(uv, iv, cv, dim, hidden)}
+            if activation == "prelu":
+                sd[f"mlp.{2 * n + 1}.weight"] = torch.full((1,), 0.25, dtype=torch.float32)
+            else:
+                sd[f"mlp.{2 * n + 1}.alpha"] = torch.tensor(float(unit), dtype=torch.float32)
+        return {k: sd[k] for k in _expected_state(uv, iv, cv, dim, hidden, activation)}
 
     def train_on_encoded(self, enc, labels, batch_size, epochs, learning_rate, order=None, init_state=None):
         """The deterministic core of ``train``: Adam over ``epochs`` passes of
@@ -440,10 +451,7 @@ class DINRanker(BaseRanker):
         if cfg.enable_negative_sampling and "label" in val_data.columns and len(val_data) > 0:
             val_data = self._apply_negative_sampling(val_data, cfg.negative_positive_ratio, "Validation Set")
         uv, iv, cv = self._prepare_vocab_dicts()
-        if cfg.din_activation != "dice" or len(cfg.din_mlp_hidden_units) != 2:
-            raise NotImplementedError("DIN training implements Dice and two MLP hidden layers; a model of another "
-                                      "depth or with PReLU, trained elsewhere, can be loaded (load_model) and "
-                                      "scored (predict)")
+        self._check_model_config(cfg.din_activation, list(cfg.din_mlp_hidden_units))
         self.user_profile_features, self.item_features, self.context_features = list(uv), list(iv), list(cv)
         self.encoder = DinEncoder(self.user_profile_dict, self.item_features_dict, self.user_history_dict,
                                   self.user_profile_features, self.item_features, self.context_features,

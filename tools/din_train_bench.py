@@ -3,12 +3,14 @@
 beside the same step as eager PyTorch on the same card.
 
 usage: python tools/din_train_bench.py [--steps 200] [--warmup 20] [--rounds 3] [--batch 256 4096] [--skip-eager]
+                                       [--hidden 200 80] [--activation dice|prelu]
 
 nrk's step is ops.din_train_grad + ops.din_adam_step (the loop body of
 DINRanker.train_on_encoded).  The eager step is the reference's way of running
 it, restated here because this tool carries no other code with it: one
 nn.Embedding per feature, the activation unit (Linear, Dice, Linear), the
-masked weighted history, the MLP with two Dice layers, sigmoid, nn.BCELoss and
+masked weighted history, the MLP (--hidden widths with Dice or nn.PReLU() per
+--activation; by default two Dice layers), sigmoid, nn.BCELoss and
 optim.Adam(lr) with torch's defaults, on batches already collated on the device
 (the reference encodes and collates on the host per batch; that cost is left
 out, in eager's favour).  The two alternate for --rounds rounds in one
@@ -50,6 +52,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batch", type=int, nargs="+", default=[256, 4096])
     ap.add_argument("--skip-eager", action="store_true")
+    ap.add_argument("--hidden", type=int, nargs="+", default=HIDDEN, help="MLP hidden widths (1 to 4)")
+    ap.add_argument("--activation", choices=["dice", "prelu"], default="dice")
     a = ap.parse_args()
     import torch
     import torch.nn as nn
@@ -82,8 +86,8 @@ def main():
             self.activation_unit = nn.Module()
             self.activation_unit.mlp = nn.Sequential(nn.Linear(4 * item_dim, 36), Dice(), nn.Linear(36, 1))
             cur, layers = (len(uf) + len(cf)) * D + 2 * item_dim, []
-            for h in HIDDEN:
-                layers += [nn.Linear(cur, h), Dice()]
+            for h in a.hidden:
+                layers += [nn.Linear(cur, h), Dice() if a.activation == "dice" else nn.PReLU()]
                 cur = h
             self.mlp = nn.Sequential(*layers, nn.Linear(cur, 1))
 
@@ -97,7 +101,8 @@ def main():
             x = torch.cat([ue, ce, re, (w * he).sum(dim=1)], dim=1)
             return torch.sigmoid(self.mlp(x)).squeeze(-1)
 
-    out = {"vocab_user": VOCAB_U, "vocab_item": VOCAB_I, "n_ctx": N_CTX, "dim": D, "hidden": HIDDEN, "seq_len": T,
+    out = {"vocab_user": VOCAB_U, "vocab_item": VOCAB_I, "n_ctx": N_CTX, "dim": D, "hidden": a.hidden, "activation": a.activation,
+           "seq_len": T,
            "device": torch.cuda.get_device_name(0), "steps": a.steps, "rounds": a.rounds}
     for B in a.batch:
         n = NB * B  # distinct batches the loops cycle through
